@@ -1,16 +1,25 @@
 """Benchmark of the recommend/top-K hot path (BASELINE.json metric) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--full]
+                    [--dump-outputs DIR]
 
 One step = one batch of B synthetic Gaussian queries through the whole path (query prep ->
 fused MFMA screen (pilot, filtered GEMM segments, merges) -> exact float64 rescore ->
 certification; for N > 1 the RCCL all-gather of the per-shard top-k + merge). The catalog (seeded Gaussian,
 generated on the GPU in fixed 65536-row blocks so every N sees the same global matrix) is
 row-sharded over the N ranks and resident in HBM before timing starts: `scaling` = "strong"
-(fixed total work). Rank 0 prints ONE JSON line. The CPU baseline (rank 0, N = 1 only) times the
-float64 oracle restatement of lib.py:51-55 -- one sklearn-style cosine_similarity + pandas sort
-per query, as the reference does -- on a bounded sample of the same queries, and the same sample
-is the parity check.
+(fixed total work). Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, the K
+timed steps, the line (metric, value, ms_per_step, the plan and the dominant kernel's roofline
+from the timed steps' own events). --dump-outputs DIR also writes what the last timed step
+returned (DIR/scores.npy, DIR/rows.npy, float64): the inputs are seeded, so two builds can be
+compared output for output. Everything else is behind --full: the top-K roofline's extra steps,
+the per-stage breakdown's extra step, the host-boundary steps, the optional device float64
+check, and the CPU baseline with the parity sample. The CPU baseline (rank 0) times the float64
+oracle restatement of lib.py:51-55 -- one sklearn-style cosine_similarity + pandas sort per
+query, as the reference does -- on a bounded sample of the same queries, and the parity sample
+checks the last timed batch against the same oracle.
 """
 from __future__ import annotations
 
@@ -37,6 +46,7 @@ METRIC = "queries/sec + top-K index match, 1M×d=1536 batch=4096, at 1/2/4/8 MI3
 PEAK_F16_TFLOPS = 2500.0   # MI355X dense bf16/f16 MFMA (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0      # HBM3E spec
 BLOCK_ROWS = 65536
+DUMP_BYTES_MAX = 64_000_000  # --dump-outputs writes at most this many bytes, file headers included
 
 
 def log(msg: str) -> None:
@@ -70,6 +80,29 @@ def make_exclusions(cfg, r: int) -> list:
     rng = np.random.default_rng(3)
     draw = rng.integers(0, cfg["n"], size=(cfg["b"], r), dtype=np.int64)
     return [np.unique(x) for x in draw]
+
+
+def dump_outputs(path: str, s: torch.Tensor, r: torch.Tensor) -> dict:
+    """--dump-outputs: what the last timed step returned to its caller -- scores f64 [B, k] and
+    rows i64 [B, k] -- as path/scores.npy and path/rows.npy, both float64 (a row id is far below
+    2^53, so exact). Above DUMP_BYTES_MAX in all, a fixed seeded sample of the queries (the same
+    for every run of the same shape), whose batch positions go to path/query_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    B = int(s.shape[0])
+    per_query = 2 * 8 * int(s.shape[1]) + 8
+    idx = None
+    budget = DUMP_BYTES_MAX - 3 * 128            # an .npy header of these arrays is 128 bytes
+    if B * per_query > budget:
+        keep = max(1, budget // per_query)
+        idx = np.sort(np.random.default_rng(4).choice(B, size=keep, replace=False))
+        sel = torch.from_numpy(idx).to(s.device)
+        s, r = s.index_select(0, sel), r.index_select(0, sel)
+        np.save(os.path.join(path, "query_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "scores.npy"), s.to(torch.float64).cpu().numpy())
+    np.save(os.path.join(path, "rows.npy"), r.to(torch.float64).cpu().numpy())
+    return {"dir": path, "arrays": ["scores", "rows"] + (["query_index"] if idx is not None else []),
+            "queries": int(s.shape[0]), "of": B,
+            "sample": None if idx is None else "seeded sample of the batch (default_rng(4))"}
 
 
 def host_info() -> dict:
@@ -566,12 +599,23 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3", choices=sorted(CONFIGS))
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU baseline work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures "
+                         "or checks: top-K roofline, per-stage breakdown, host boundary, CPU "
+                         "baseline + parity sample, --device-check (a plain run only times)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/scores.npy and "
+                         "DIR/rows.npy (float64; a seeded sample of the queries above 64 MB)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0,
+                    help="(--full) seconds of CPU baseline work")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="(--full) leave out the CPU baseline and the parity sample")
     ap.add_argument("--parity", type=int, default=0,
-                    help="queries in the host-oracle parity sample (0 = 128, 32 above 1M rows)")
+                    help="(--full) queries in the host-oracle parity sample (0 = 128, 32 above "
+                         "1M rows)")
     ap.add_argument("--device-check", type=int, default=0,
-                    help="(N = 1) also check this many queries against torch float64 on the GPU")
+                    help="(--full, N = 1) also check this many queries against torch float64 "
+                         "on the GPU")
     ap.add_argument("--n", type=int, default=None, help="override catalog rows (experiments)")
     ap.add_argument("--b", type=int, default=None, help="override batch (experiments)")
     ap.add_argument("--streams", type=int, default=1,
@@ -604,6 +648,9 @@ def main() -> None:
 
     if args.gpus < 1:
         log("error: --gpus must be >= 1")
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        log("error: --steps must be >= 1 and --warmup >= 0")
         sys.exit(2)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no external launcher: this process only starts the ranks (before any GPU call)
@@ -727,7 +774,7 @@ def main() -> None:
     pl = plan(cat, cfg["b"], k)
     # inside the timed region only the dominant kernel's launches are bracketed by hipEvents
     # (every recorded stage adds ~5 us of stream gaps); the per-stage breakdown comes from one
-    # extra, untimed step below
+    # extra, untimed step below (--full)
     dom_stage = "gemm_filter" if pl["fused"] else "gemm"
     timer.reset()
     timer.only(dom_stage)
@@ -746,19 +793,27 @@ def main() -> None:
         elapsed = float(t.item())
 
     dom_ms, dom_n = timer.query(dom_stage)
-    topk = measure_topk(run_steps, timer, dev, max(1, min(args.steps, 10)), pl["kprime"], cfg,
-                        emb.element_size())
-    topk["traffic"], tk = pmc_kernel_traffic(args.config, world, "rescore_kernel")
-    topk["traffic_note"] = (f"profiles/pmc_{args.config}_n{world}.json ({tk}): FETCH_SIZE x 2 + "
-                            "WRITE_SIZE per launch, separate --pmc passes" if tk else
-                            "no rescore entry in this config's PMC summary")
-    timer.reset()
-    timer.only()
-    run_steps(1)
-    torch.cuda.synchronize(dev)
-    from robot_ebert_amd._lib import STAGES
-    st = {name: timer.query(name) for name in STAGES}
-    host = host_boundary(cat, k, q, timer) if world == 1 else None
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, s, r)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+    topk, st, host = None, None, None
+    if args.full:
+        # runs of their own, after the timed region: the top-K roofline's steps, one step with
+        # every stage bracketed, the host-boundary steps
+        topk = measure_topk(run_steps, timer, dev, max(1, min(args.steps, 10)), pl["kprime"],
+                            cfg, emb.element_size())
+        topk["traffic"], tk = pmc_kernel_traffic(args.config, world, "rescore_kernel")
+        topk["traffic_note"] = (f"profiles/pmc_{args.config}_n{world}.json ({tk}): FETCH_SIZE x "
+                                "2 + WRITE_SIZE per launch, separate --pmc passes" if tk else
+                                "no rescore entry in this config's PMC summary")
+        timer.reset()
+        timer.only()
+        run_steps(1)
+        torch.cuda.synchronize(dev)
+        from robot_ebert_amd._lib import STAGES
+        st = {name: timer.query(name) for name in STAGES}
+        host = host_boundary(cat, k, q, timer) if world == 1 else None
     n_local = end - begin
     B, d = cfg["b"], cfg["d"]
     head = pl["head_rows"]
@@ -775,7 +830,7 @@ def main() -> None:
         dom_name = "screen_gemm_qp2_kernel<store>"
         dom_flops = 2.0 * B * n_local * d * args.steps
     achieved = dom_flops / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else None
-    all_gemm_ms = st["gemm"][0] + st["gemm_filter"][0]   # the extra step
+    all_gemm_ms = st["gemm"][0] + st["gemm_filter"][0] if st else 0   # the extra step (--full)
     all_tf = 2.0 * B * n_local * d / (all_gemm_ms * 1e-3) / 1e12 if all_gemm_ms else None
     value = cfg["b"] * args.steps / elapsed
     traffic, traffic_note = pmc_traffic(args.config, world)
@@ -825,25 +880,29 @@ def main() -> None:
                                "flops_formula": "2*B*rows*d per launch (rows = the launch's segment "
                                                 "of the fused screen; averaged over the "
                                                 "segments)"},
-                "all_gemm_tflops": round(all_tf, 2) if all_tf else None,
+                "all_gemm_tflops": round(all_tf, 2) if all_tf else None,   # --full
                 "per_n": "rank 0's own launches of the dominant kernel over its shard "
                          "(n_local rows); traffic from the committed PMC summary for this "
                          "config and N (profiles/pmc_<config>_n<N>.json), null when none",
             },
-            "roofline_topk": topk,
             "plan": pl,
-            "stage_ms_per_step": {name: round(v[0], 4) for name, v in st.items()},
-            "stage_breakdown": stage_breakdown(st, pl_ms, world),
-            "host_boundary": host,
+            "full": args.full,
+            "outputs": dumped,
         }
         out["roofline"]["traffic_note"] = traffic_note
-        if args.no_cpu_baseline:
+        if args.full:
+            out["roofline_topk"] = topk
+            out["stage_ms_per_step"] = {name: round(v[0], 4) for name, v in st.items()}
+            out["stage_breakdown"] = stage_breakdown(st, pl_ms, world)
+            out["host_boundary"] = host
+        # a plain run has no CPU baseline, no parity sample and no device check
+        if args.full and args.no_cpu_baseline:
             out["cpu_baseline"] = None
-        elif world == 1:
+        elif args.full and world == 1:
             out["cpu_baseline"], out["parity"] = cpu_baseline_and_parity(
                 cfg, lambda rows: host_blocks(emb, rows), emb.shape[0], q, s, r,
                 args.cpu_budget, args.parity, exclude=excl_lists)
-        else:
+        elif args.full:
             # N > 1: rank 0 holds only its shard; the CPU baselines and the parity sample (the
             # merged global top-k of the last timed batch) run over the WHOLE catalog,
             # regenerated block by block from its seeds on rank 0's GPU
@@ -856,7 +915,7 @@ def main() -> None:
         if args.share_gpu and world > 1:
             out["rehearsal"] = (f"{world} ranks sharing GPU 0 over gloo: the multi-process "
                                 "sharded path end to end, NOT a scaling measurement")
-        if world == 1 and args.device_check > 0:
+        if args.full and world == 1 and args.device_check > 0:
             out["device_parity"] = device_f64_check(emb, q, s, r, args.device_check)
         print(json.dumps(out), flush=True)
     if rccl is not None:

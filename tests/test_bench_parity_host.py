@@ -123,3 +123,31 @@ def test_line_dtype_is_the_result_arithmetic():
         assert lab["dtype"] == "f64"
         assert lab["screen_operands"] == ops
         assert "f64" in lab["arith"] and ops in lab["arith"] and "certified" in lab["arith"]
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's (scores f64, rows i64) as float64 .npy files,
+    whole below the byte limit; above it the same seeded sample of the queries on every call,
+    with their batch positions beside them, and never more than the limit in all."""
+    g = torch.Generator().manual_seed(7)
+    s = torch.randn((50, 8), generator=g, dtype=torch.float64)
+    r = torch.randint(0, 1 << 40, (50, 8), generator=g, dtype=torch.int64)
+    info = bench.dump_outputs(str(tmp_path / "a"), s, r)
+    assert info["queries"] == 50 and info["sample"] is None
+    assert sorted(os.listdir(tmp_path / "a")) == ["rows.npy", "scores.npy"]
+    gs, gr = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "rows.npy")
+    assert gs.dtype == np.float64 and gr.dtype == np.float64
+    assert np.array_equal(gs, s.numpy()) and np.array_equal(gr.astype(np.int64), r.numpy())
+    # 50 queries x (8 x 16 + 8) bytes = 6800 > 2048: a sample of (2048 - 3 x 128) // 136 = 12
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 2048)
+    for name in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / name), s, r)
+        assert info["queries"] == 12 and info["of"] == 50
+    files = [np.load(tmp_path / "b" / f"{a}.npy") for a in ("query_index", "scores", "rows")]
+    again = [np.load(tmp_path / "c" / f"{a}.npy") for a in ("query_index", "scores", "rows")]
+    assert all(np.array_equal(x, y) for x, y in zip(files, again))
+    idx = files[0].astype(np.int64)
+    assert len(np.unique(idx)) == 12 and np.all(np.diff(idx) > 0) and idx.max() < 50
+    assert np.array_equal(files[1], s.numpy()[idx])
+    assert np.array_equal(files[2].astype(np.int64), r.numpy()[idx])
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 2048

@@ -1,4 +1,4 @@
-"""GPU: the row-sharded path as real processes (`bench.py --gpus 2 --share-gpu`).
+"""GPU: the row-sharded path as real processes (`bench.py --gpus 2 --share-gpu --full`).
 
 bench.py starts two ranks itself; both use GPU 0 and exchange the shared threshold, the
 catalog-wide floor and the per-shard top-k over gloo (a one-GPU box cannot run two RCCL ranks).
@@ -30,7 +30,7 @@ def test_bench_processes_share_gpu(cuda_device, world, n, b):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, BENCH, "--gpus", str(world), "--share-gpu", "--config",
                         "C3", "--n", str(n), "--b", str(b), "--steps", "2", "--warmup", "1",
-                        "--cpu-budget", "1", "--collective-timeout", "120",
+                        "--full", "--cpu-budget", "1", "--collective-timeout", "120",
                         "--launch-timeout", "280"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, p.stderr[-4000:]

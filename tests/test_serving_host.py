@@ -275,13 +275,25 @@ def test_cancelled_future_does_not_stop_the_client():
     b.close()
 
 
-def test_garbled_server_frame_fails_pending_callers(tmp_path):
+@pytest.fixture
+def sock_dir():
+    """A short directory for a socket file: an AF_UNIX path holds about 107 bytes, and pytest's
+    tmp_path under a deep temporary root is longer (ScoreServer's own default is under /tmp
+    too)."""
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="ebt-", dir="/tmp")
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+def test_garbled_server_frame_fails_pending_callers(sock_dir):
     """A frame from the server that does not decode ends the client's connection: its pending
     and later callers get a RuntimeError instead of waiting forever (the reader thread must not
     die with callers registered)."""
     from multiprocessing.connection import Listener
     from robot_ebert_amd.serving import AUTHKEY
-    addr = str(tmp_path / "fake.sock")
+    addr = os.path.join(sock_dir, "fake.sock")
     lst = Listener(addr, family="AF_UNIX", authkey=AUTHKEY)
     got = {}
 

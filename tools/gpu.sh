@@ -4,7 +4,8 @@
 # the first failure.
 #   suite  OUT                 the whole -m gpu suite, then __graft_entry__.smoke()
 #   tests  OUT EXPR [FILES..]  pytest -m gpu -k EXPR over FILES (default tests/)
-#   bench  OUT CONFIG [ARGS..] bench.py --config CONFIG ARGS -> OUT/bench_CONFIG.json (+ .log)
+#   bench  OUT CONFIG [ARGS..] bench.py --config CONFIG ARGS -> OUT/bench_CONFIG.json (+ .log);
+#                              --full among ARGS for the whole line (parity, stages, baselines)
 #   prof   OUT CONFIG [STEPS]  rocprofv3 kernel-trace + stats, then FETCH_SIZE and WRITE_SIZE
 #                              PMC passes (one counter block each) on the screening GEMM and the
 #                              rescore (the top-K roofline's kernel)
@@ -167,10 +168,10 @@ EOF
       r4_sample)   $G ab r4s_d40 _abl/libebert_div40.so C3,C4; $G ab r4s_d30 _abl/libebert_div30.so C3 ;;
       r4_stage)    $G suite r4g; $G epi r4g_epi epi_old epi; $G ab r4g _abl/libebert_head.so C2,C3 ;;
       r4_stores)   $G stamp r4s stamp stamp_nohit stamp_nocnt stamp_none ;;
-      r4_final)    $G suite r4f; $G bench r4f C3 --steps 20; $G bench r4f C2 --steps 50
+      r4_final)    $G suite r4f; $G bench r4f C3 --steps 20 --full; $G bench r4f C2 --steps 50 --full
                    $G prof r4f_prof C3 5
-                   $G bench r4f C4 --steps 5 --warmup 1 --parity 32
-                   $G bench r4f C5 --steps 3 --warmup 1 --parity 32 ;;
+                   $G bench r4f C4 --steps 5 --warmup 1 --parity 32 --full
+                   $G bench r4f C5 --steps 3 --warmup 1 --parity 32 --full ;;
       r4_prof_c45) $G prof r4p_c4 C4 3; $G prof r4p_c5 C5 2 ;;
       # round 5 (profiles/r5/README.md)
       r5_lead)     $G ab r5c_ab EBT_SPEC_LEAD=0 C2,C3 2 ;;
@@ -196,12 +197,12 @@ EOF
                    $G py r5m_rs1 tools/rank_sim_capi.py --config C3 --world 8 --steps 20 ;;
       r5_segrate)  $G ab r5s_ab _abl/libebert_prev.so C3 3 ;;
       r5_nr8)      $G ab r5u_ab _abl/libebert_nr8.so C2 3 ;;               # -DEBT_RESCORE_NR_NARROW=8
-      r5_final)    $G suite r5t; $G bench r5t C3 --steps 20
+      r5_final)    $G suite r5t; $G bench r5t C3 --steps 20 --full
                    $G py r5t_rs tools/rank_sim_capi.py --config C3 --world 8 --steps 20
                    $G prof r5t_prof C3 5
-                   $G bench r5r_c4 C4 --steps 10; $G bench r5r_c5 C5 --steps 5 --warmup 2
-                   $G bench r5r_n2 C3 --gpus 2 --share-gpu --steps 5 --warmup 2 --cpu-budget 4
-                   $G bench r5r_n4 C3 --gpus 4 --share-gpu --steps 5 --warmup 2 --cpu-budget 4 ;;
+                   $G bench r5r_c4 C4 --steps 10 --full; $G bench r5r_c5 C5 --steps 5 --warmup 2 --full
+                   $G bench r5r_n2 C3 --gpus 2 --share-gpu --steps 5 --warmup 2 --cpu-budget 4 --full
+                   $G bench r5r_n4 C3 --gpus 4 --share-gpu --steps 5 --warmup 2 --cpu-budget 4 --full ;;
       *) echo "unknown recipe $N" >&2; exit 2 ;;
     esac
     ;;
