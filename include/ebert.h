@@ -70,7 +70,10 @@ extern "C" {
  * 0.3.3: a pinned certificate buffer of ebt_cosine_topk_submit / ebt_cosine_topk_sharded_submit
  *        is written by the kernels themselves (no copy launch; EBT_EHIP from _finish if one was
  *        not delivered); the speculative screen's segment thresholds come from its wave merges;
- *        ebt_merge_packed also flags a query with more than min(R k, 2 k + 256) entries. */
+ *        ebt_merge_packed also flags a query with more than min(R k, 2 k + 256) entries.
+ * 0.4.0: live catalog updates: ebt_catalog_init_reserved, ebt_catalog_update_bytes,
+ *        ebt_catalog_update_rows, ebt_catalog_append_rows (additive; struct ebt_catalog and
+ *        ebt_catalog_init are unchanged). */
 int ebt_version(void);
 
 /* Message for the last non-zero return on this thread ("" if none). */
@@ -373,7 +376,8 @@ int ebt_cosine_topk_prepared(const double* q64, const void* qimg, const float* q
  * ebt_catalog: the resident (shard of a) catalog, filled by ebt_catalog_init from the caller's
  * device matrix and a caller-provided device STATE buffer of ebt_catalog_state_bytes() bytes
  * (float64 guarded row norms, float32 inverse norms, and the f16 screening image unless the
- * matrix itself is the MFMA operand: f16 / bf16 with d, ld % 64 == 0). Immutable afterwards;
+ * matrix itself is the MFMA operand: f16 / bf16 with d, ld % 64 == 0). Afterwards it changes
+ * only through the live-update entries below (0.4.0), which rewrite rows and their state in place;
  * the struct and the state buffer must outlive every call that uses them. For a non-native
  * catalog (f32 / f64) ebt_catalog_init waits for `stream` once, to read back u_cat, the largest
  * row error of the image its kernel measured (0.3.1); a native catalog's init stays asynchronous. */
@@ -394,6 +398,57 @@ size_t ebt_catalog_state_bytes(const void* data, int dtype, int64_t n, int32_t d
 int ebt_catalog_init(ebt_catalog* cat, const void* data, int dtype, int64_t n, int32_t d,
                      int64_t ld, int64_t row_offset, void* state, size_t state_bytes,
                      void* stream);
+
+/* ---- live updates (0.4.0): replace and append rows in place --------------------------------
+ * A catalog that is to grow is initialised with room: `data` holds n_cap >= n rows, `state` is
+ * sized by ebt_catalog_state_bytes(data, dtype, n_cap, d, ld) and laid out for n_cap rows, and
+ * the first n rows are initialised exactly as ebt_catalog_init would (which is the n_cap == n
+ * case); inv32[n .. round_up(n_cap, 128)) = 1.0f. The struct describes the first n rows. */
+int ebt_catalog_init_reserved(ebt_catalog* cat, const void* data, int dtype, int64_t n,
+                              int64_t n_cap, int32_t d, int64_t ld, int64_t row_offset,
+                              void* state, size_t state_bytes, void* stream);
+
+/* Device scratch of ebt_catalog_update_rows for a list of m rows: round_up(8 m, 256) bytes
+ * (0 for m <= 0). */
+size_t ebt_catalog_update_bytes(int64_t m);
+
+/* Replace m rows: ONE kernel reads each source row once, converts it to the catalog's dtype
+ * (round-to-nearest-even; to f16 / bf16 through float, as torch's .to(dtype)), writes it into
+ * `data` (the catalog's matrix is written: it must be writable device memory) and recomputes
+ * that row's gnorm64, inv32, image row and -- for a non-native catalog -- image error, with the
+ * arithmetic and summation order of ebt_catalog_init: afterwards the state is bit-identical to
+ * that of a catalog initialised from the edited matrix.
+ *   state, state_bytes, n_cap: what ebt_catalog_init(_reserved) was given (n_cap = n for
+ *     ebt_catalog_init). The state's layout is derived from n_cap; if cat's pointers do not
+ *     match it (a hand-filled struct, another capacity) the call returns EBT_EINVAL. (The
+ *     struct does not record the error slot behind the image: an n_cap within the same 32 rows
+ *     of the true one moves only that and is not detected. Pass the value given at init.)
+ *   rows: HOST pointer, m GLOBAL row ids, strictly ascending, all in [row_offset, row_offset + n).
+ *   src: device, m rows of d elements of src_dtype (any of the four), row stride ld_src elements;
+ *     it must not overlap `data`.
+ *   ws: device scratch of ebt_catalog_update_bytes(m) bytes (the row list).
+ * Every argument check (the order and range of `rows` included) runs on the host before any GPU
+ * call; a failed check returns EBT_EINVAL and leaves the catalog and *cat unchanged. m == 0 is
+ * EBT_OK and does nothing.
+ * u_cat: a native catalog's update is fully asynchronous and u_cat stays 0. A non-native one
+ * waits for `stream` once to read the error slot back, as ebt_catalog_init does, and sets
+ * cat->u_cat to it. The slot holds the RUNNING maximum over every row the catalog ever held: it
+ * never decreases, and a replaced row's old error may keep it larger than that of a fresh
+ * ebt_catalog_init of the same matrix -- still a valid bound (any value up to 2^-11 is).
+ * Ordering: an update is stream-ordered. A batch submitted on the same stream BEFORE the update
+ * sees the old catalog, one submitted after it the new one. A batch whose _finish has not
+ * returned must be finished before an update is issued: its retries would run after the update
+ * and reuse an eps computed from the old u_cat. */
+int ebt_catalog_update_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
+                            const int64_t* rows, int64_t m, const void* src, int src_dtype,
+                            int64_t ld_src, void* ws, size_t ws_bytes, void* stream);
+
+/* The same kernel on local rows n .. n + m - 1 (global row_offset + n ..), then cat->n += m.
+ * EBT_EINVAL if n + m > n_cap. Workspaces sized by ebt_workspace_bytes for the smaller n may be
+ * too small afterwards: size them again (or for n_cap from the start). */
+int ebt_catalog_append_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
+                            int64_t m, const void* src, int src_dtype, int64_t ld_src,
+                            void* stream);
 
 /* Optional knobs (NULL = defaults; a zero field = its default): kprime = the screen's candidate
  * count k' (default: k + slack for the image's error band), chunk_rows = catalog rows per

@@ -3,6 +3,10 @@
 The hot path (query x catalog cosine + top-k, reference src/backend/app/lib.py:51-55) runs in
 hand-written HIP kernels for gfx950 behind the C ABI of include/ebert.h (libebert.so, loaded by
 ctypes). Python keeps the reference's call surface: ``lib.get_user_recs`` and friends.
+
+The resident ``Catalog`` is live: ``Catalog.update_rows`` / ``Catalog.append`` (ABI 0.4.0) replace
+and append rows in place; ``RecBatcher.update_rows`` / ``.append`` do so between batches and
+``distributed.split_update`` hands each shard of a row-sharded catalog its part of an update.
 """
 from ._lib import EbertError, Timer, load  # noqa: F401
 from .catalog import Catalog  # noqa: F401

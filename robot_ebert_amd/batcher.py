@@ -22,6 +22,11 @@ concurrently, SURVEY §8b "Threading") only the dispatcher does.
 * Bounded statistics: ``batches`` keeps the sizes of the last ``history`` batches; ``stats()``
   gives totals and a power-of-two batch-size histogram.
 
+* Live updates: ``update_rows`` / ``append`` hand a catalog edit to the dispatcher, which treats it
+  as a barrier: everything queued before it is dispatched, every in-flight batch is finished,
+  the edit is applied, then collection resumes (ebert.h: an update must not overtake a batch
+  whose finish has not returned).
+
 Per-request semantics are those of ``lib.get_user_recs``: a request without liked rows fails
 with sklearn's ValueError (alone -- the rest of its batch is unaffected), results are
 (scores float64, global rows int64) ordered (score desc, row asc).
@@ -55,6 +60,14 @@ def _answer(fut: Future, result=None, exc: Optional[BaseException] = None) -> No
             fut.set_result(result)
     except Exception:  # noqa: BLE001 -- InvalidStateError: cancelled in between
         pass
+
+
+class _Update:
+    """A catalog edit in the request queue: (method name, arguments, the caller's Future)."""
+    __slots__ = ("method", "args", "fut")
+
+    def __init__(self, method: str, args: tuple, fut: Future) -> None:
+        self.method, self.args, self.fut = method, args, fut
 
 
 def k_class(k: int) -> int:
@@ -161,6 +174,26 @@ class RecBatcher:
             self._q.put(item)
         return fut
 
+    def update_rows(self, rows, vectors) -> Future:
+        """``catalog.update_rows(rows, vectors)`` as a barrier between requests: those queued
+        before this call are scored against the old catalog, those submitted after the Future
+        resolves (to None, or the update's error) against the new one."""
+        return self._edit("update_rows", (rows, vectors))
+
+    def append(self, vectors, ids=None) -> Future:
+        """``catalog.append(vectors, ids)`` under the same barrier; requests submitted after
+        the Future resolves are validated against the new n."""
+        return self._edit("append", (vectors, ids))
+
+    def _edit(self, method: str, args: tuple) -> Future:
+        fut: Future = Future()
+        with self._lock:
+            if self._closed:
+                fut.set_exception(RuntimeError("batcher is closed"))
+                return fut
+            self._q.put(_Update(method, args, fut))
+        return fut
+
     def close(self, timeout: Optional[float] = 10.0) -> None:
         """Stop accepting requests, finish the queued ones, join the dispatcher."""
         with self._lock:
@@ -179,10 +212,14 @@ class RecBatcher:
                 "size_hist_pow2": dict(sorted(self._hist.items()))}
 
     # ---- dispatcher thread ---------------------------------------------------------------------
-    def _collect(self) -> Tuple[list, bool]:
+    def _collect(self) -> Tuple[list, bool, Optional[_Update]]:
+        """The next batch's requests, whether close() was seen, and the catalog edit that ended
+        the collection (nothing queued behind an edit joins a batch in front of it)."""
         first = self._q.get()
         if first is _SENTINEL:
-            return [], True
+            return [], True, None
+        if isinstance(first, _Update):
+            return [], False, first
         reqs = [first]
         deadline = time.monotonic() + self.max_wait
         stop = False
@@ -195,30 +232,56 @@ class RecBatcher:
             if item is _SENTINEL:
                 stop = True
                 break
+            if isinstance(item, _Update):
+                return reqs, False, item
             reqs.append(item)
-        return reqs, stop
+        return reqs, stop, None
 
     def _run(self) -> None:
         if self._pipelined:
             self._bind_device()
         while True:
-            reqs, stop = self._collect()
+            reqs, stop, edit = self._collect()
             if reqs:
                 groups: Dict[int, list] = collections.defaultdict(list)
                 for r in reqs:
                     groups[k_class(r[2])].append(r)
                 for c in sorted(groups):
                     self._dispatch_safe(groups[c])
+            if edit is not None:
+                self._apply_edit(edit)
             if stop:
                 while True:  # drain what was queued before close()
                     try:
                         item = self._q.get_nowait()
                     except queue.Empty:
                         break
-                    if item is not _SENTINEL:
+                    if isinstance(item, _Update):
+                        self._apply_edit(item)
+                    elif item is not _SENTINEL:
                         self._dispatch_safe([item])
                 self._done.put(_SENTINEL)
                 return
+
+    def _apply_edit(self, edit: _Update) -> None:
+        """The barrier: every batch dispatched so far is finished (all the in-flight permits
+        taken: the completion thread returns one per finished batch), the edit runs on this
+        thread -- the one that submits the batches, so on their stream -- and the permits go back.
+        With an injected score_fn batches run synchronously here: nothing is in flight."""
+        held = 0
+        try:
+            if self._pipelined:
+                for _ in range(self.max_inflight):
+                    self._slots.acquire()
+                    held += 1
+            result = getattr(self.catalog, edit.method)(*edit.args)
+        except BaseException as e:  # noqa: BLE001 -- the edit's error goes to its caller
+            _answer(edit.fut, exc=e)
+        else:
+            _answer(edit.fut, result)
+        finally:
+            for _ in range(held):
+                self._slots.release()
 
     def _record(self, n: int) -> None:
         self.batches.append(n)

@@ -49,10 +49,15 @@ class Catalog:
     ids : optional sequence of string ids (the DataFrame index of constants.py:56), one per row.
     row_offset : global row id of local row 0 when the catalog is row-sharded across ranks.
     n_global : total rows over all shards (defaults to n).
+    capacity : optional row capacity >= n. The catalog then owns a ``[capacity, d]`` copy of
+        ``emb`` and a state laid out for ``capacity`` rows, so that ``append`` can grow it in
+        place; every attribute still describes the first n rows. Without it the catalog views
+        ``emb`` itself (``update_rows`` then writes into that tensor) and cannot grow.
     """
 
     def __init__(self, emb: torch.Tensor, ids: Optional[Sequence[str]] = None,
-                 row_offset: int = 0, n_global: Optional[int] = None) -> None:
+                 row_offset: int = 0, n_global: Optional[int] = None,
+                 capacity: Optional[int] = None) -> None:
         require_cuda(emb, "catalog embeddings")
         if emb.dim() != 2 or emb.shape[0] < 1 or emb.shape[1] < 1:
             raise EbertError(f"catalog must be a non-empty 2-D matrix, got {tuple(emb.shape)}")
@@ -60,6 +65,15 @@ class Catalog:
             raise EbertError(f"unsupported catalog dtype {emb.dtype}")
         if emb.stride(1) != 1:
             emb = emb.contiguous()
+        self._store = emb   # the rows' storage: emb itself, or [capacity, d] owned here
+        if capacity is not None:
+            capacity = int(capacity)
+            if capacity < emb.shape[0]:
+                raise EbertError(f"capacity {capacity} < {emb.shape[0]} rows")
+            self._store = torch.empty((capacity, emb.shape[1]), dtype=emb.dtype,
+                                      device=emb.device)
+            self._store[:emb.shape[0]].copy_(emb)
+            emb = self._store[:emb.shape[0]]
         self.data = emb
         self.device = emb.device
         self.n, self.d = int(emb.shape[0]), int(emb.shape[1])
@@ -71,33 +85,146 @@ class Catalog:
         # the C ABI's catalog (ebt_catalog_init): guarded float64 norms, float32 inverse norms
         # and the screening image in one device state buffer owned here
         lib = _lib.load()
-        need = lib.ebt_catalog_state_bytes(ptr(emb), self.dtype_code, self.n, self.d, self.ld)
+        self.capacity = capacity if capacity is not None else self.n
+        need = lib.ebt_catalog_state_bytes(ptr(emb), self.dtype_code, self.capacity, self.d,
+                                           self.ld)
         if need == 0:
             raise EbertError(f"bad catalog shape {tuple(emb.shape)} (ld {self.ld})")
         self.state = torch.empty(need, dtype=torch.uint8, device=self.device)
         self.cstruct = _lib.EbtCatalog()
-        call("ebt_catalog_init", ctypes.byref(self.cstruct), ptr(emb), self.dtype_code, self.n,
-             self.d, self.ld, self.row_offset, ptr(self.state), need, stream_of(self.device))
+        if capacity is None:
+            call("ebt_catalog_init", ctypes.byref(self.cstruct), ptr(emb), self.dtype_code, self.n,
+                 self.d, self.ld, self.row_offset, ptr(self.state), need, stream_of(self.device))
+        else:
+            call("ebt_catalog_init_reserved", ctypes.byref(self.cstruct), ptr(emb),
+                 self.dtype_code, self.n, self.capacity, self.d, self.ld, self.row_offset,
+                 ptr(self.state), need, stream_of(self.device))
         c = self.cstruct
-        off_inv = _al(self.n * 8)
-        n128 = _round_up(self.n, 128)
-        off_img = off_inv + _al(n128 * 4)
-        self.gnorm = self.state[:self.n * 8].view(torch.float64)
-        self.inv32 = self.state[off_inv:off_inv + n128 * 4].view(torch.float32)
         self.img_dtype = int(c.img_dtype)
         self.ld_img = int(c.ld_img)
         self.native = bool(c.native)
-        self.u_cat = float(c.u_cat)
-        self.cscale = self.inv32 if self.native else None
-        if c.image == emb.data_ptr():
-            self.image = emb  # the matrix itself is the MFMA operand
-        else:
-            self.image = self.state[off_img:off_img + self.n * self.ld_img * 2].view(
-                self.img_torch_dtype).view(self.n, self.ld_img)
+        self._views()
         self.ids: Optional[List[str]] = list(ids) if ids is not None else None
         if self.ids is not None and len(self.ids) != self.n:
             raise EbertError(f"{len(self.ids)} ids for {self.n} rows")
         self._pos: Optional[Dict[str, int]] = None
+
+    def _views(self) -> None:
+        """The tensors the scoring code reads, over the first n rows of a state laid out for
+        ``capacity`` rows (ebt_catalog_init_reserved; capacity == n: ebt_catalog_init)."""
+        c = self.cstruct
+        self.n = int(c.n)
+        self.data = self._store if self.n == self._store.shape[0] else self._store[:self.n]
+        off_inv = _al(self.capacity * 8)
+        off_img = off_inv + _al(_round_up(self.capacity, 128) * 4)
+        n128 = _round_up(self.n, 128)
+        self.gnorm = self.state[:self.n * 8].view(torch.float64)
+        self.inv32 = self.state[off_inv:off_inv + n128 * 4].view(torch.float32)
+        self.u_cat = float(c.u_cat)
+        self.cscale = self.inv32 if self.native else None
+        if c.image == self._store.data_ptr():
+            self.image = self.data  # the matrix itself is the MFMA operand
+        else:
+            self.image = self.state[off_img:off_img + self.n * self.ld_img * 2].view(
+                self.img_torch_dtype).view(self.n, self.ld_img)
+
+    # ---- live updates (ebt_catalog_update_rows / ebt_catalog_append_rows) -----------------
+    def _vectors(self, vectors, m: Optional[int]) -> torch.Tensor:
+        """The update's source rows as a device tensor [m, d] of a supported dtype, checked."""
+        if self.state is None:
+            raise EbertError("a from_parts catalog cannot be updated: its norms and image are "
+                             "the caller's tensors, not a state this library laid out")
+        if isinstance(vectors, np.ndarray):
+            vectors = torch.from_numpy(np.ascontiguousarray(vectors))
+        if not isinstance(vectors, torch.Tensor) or vectors.dim() != 2:
+            raise EbertError("vectors must be a 2-D tensor or numpy array [m, d]")
+        if vectors.dtype not in DTYPE_CODE:
+            raise EbertError(f"unsupported vector dtype {vectors.dtype}")
+        if int(vectors.shape[1]) != self.d:
+            raise EbertError(f"vectors have d = {int(vectors.shape[1])}, the catalog {self.d}")
+        if m is not None and int(vectors.shape[0]) != m:
+            raise EbertError(f"{int(vectors.shape[0])} vectors for {m} rows")
+        return vectors
+
+    def update_rows(self, rows_or_ids, vectors) -> None:
+        """Replace rows in place: ``rows_or_ids`` are GLOBAL rows or string ids, ``vectors`` a
+        tensor or numpy array [m, d] of any supported dtype (converted as ``.to(dtype)``). One
+        kernel rewrites the rows, their norms and image rows; the state afterwards equals that
+        of a catalog built from the edited matrix, except that ``u_cat`` never decreases.
+        Stream-ordered on the current stream; every batch submitted before it must have been
+        finished (include/ebert.h, "Ordering"). Bad arguments raise EbertError before any GPU
+        work and leave the catalog unchanged."""
+        items = list(rows_or_ids)
+        vectors = self._vectors(vectors, len(items))
+        if any(isinstance(t, str) for t in items):
+            try:
+                rows = self.rows_of(items)
+            except KeyError as e:
+                raise EbertError(f"unknown id {e}") from e
+        else:
+            try:
+                rows = [int(r) for r in items]
+            except (TypeError, ValueError) as e:
+                raise EbertError(f"malformed rows: {e}") from e
+        lo, hi = self.row_offset, self.row_offset + self.n
+        for r in rows:
+            if r < lo or r >= hi:
+                raise EbertError(f"row {r} is not in the catalog rows [{lo}, {hi})")
+        if len(set(rows)) != len(rows):
+            raise EbertError("duplicate rows in one update")
+        m = len(rows)
+        if m == 0:
+            return
+        order = sorted(range(m), key=rows.__getitem__)
+        vectors = vectors.to(self.device)
+        if order != list(range(m)):   # the library takes ascending rows: permute the vectors alike
+            vectors = vectors[torch.tensor(order, dtype=torch.int64, device=self.device)]
+        elif vectors.stride(1) != 1:
+            vectors = vectors.contiguous()
+        host_rows = np.asarray([rows[i] for i in order], dtype=np.int64)
+        lib = _lib.load()
+        ws = torch.empty(lib.ebt_catalog_update_bytes(m), dtype=torch.uint8, device=self.device)
+        call("ebt_catalog_update_rows", ctypes.byref(self.cstruct), ptr(self.state),
+             self.state.numel(), self.capacity, host_rows.ctypes.data, m, ptr(vectors),
+             DTYPE_CODE[vectors.dtype], int(vectors.stride(0)), ptr(ws), ws.numel(),
+             stream_of(self.device))
+        self.u_cat = float(self.cstruct.u_cat)
+
+    def append(self, vectors, ids: Optional[Sequence[str]] = None) -> None:
+        """Append rows in place, up to ``capacity``: n, n_global, the C struct, the ids and the
+        id -> row map grow together. ``ids`` is required iff the catalog has ids. Refused on a
+        row-sharded catalog. Ordering as for ``update_rows``."""
+        vectors = self._vectors(vectors, None)
+        if self.row_offset != 0 or self.n_global != self.n:
+            raise EbertError("append on a row-sharded catalog is not supported")
+        m = int(vectors.shape[0])
+        if (ids is not None) != (self.ids is not None):
+            raise EbertError("append needs ids exactly when the catalog has ids")
+        if ids is not None:
+            ids = list(ids)
+            if len(ids) != m:
+                raise EbertError(f"{len(ids)} ids for {m} rows")
+            pos = self.index_pos
+            if len(set(ids)) != m or any(t in pos for t in ids):
+                raise EbertError("append: an id is already in the catalog (or given twice)")
+        if self.n + m > self.capacity:
+            raise EbertError(f"append of {m} rows to {self.n} exceeds the capacity "
+                             f"{self.capacity} (construct the Catalog with capacity=)")
+        if m == 0:
+            return
+        vectors = vectors.to(self.device)
+        if vectors.stride(1) != 1:
+            vectors = vectors.contiguous()
+        first = self.n
+        call("ebt_catalog_append_rows", ctypes.byref(self.cstruct), ptr(self.state),
+             self.state.numel(), self.capacity, m, ptr(vectors), DTYPE_CODE[vectors.dtype],
+             int(vectors.stride(0)), stream_of(self.device))
+        self._views()
+        self.n_global = self.n
+        if ids is not None:
+            self.ids.extend(ids)
+            for i, t in enumerate(ids):
+                self._pos[t] = first + i
 
     # ---- constructors ---------------------------------------------------------------------
     @classmethod
@@ -154,7 +281,8 @@ class Catalog:
         self.u_cat = 0.0 if native_16 else 2.0 ** -11
         self.cscale = self.inv32 if native_16 else None
         self.ids, self._pos = None, None
-        self.state = None
+        self.state = None   # no state of the library's layout: update_rows / append refuse
+        self._store, self.capacity = self.data, self.n
         self.cstruct = _lib.EbtCatalog(
             data=ptr(self.data), dtype=self.dtype_code, d=self.d, n=self.n, ld=self.ld,
             row_offset=self.row_offset, gnorm64=ptr(gnorm), inv32=ptr(inv32), image=ptr(image),

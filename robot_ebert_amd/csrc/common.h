@@ -65,6 +65,26 @@ __device__ __forceinline__ uint16_t f64_to_img(double v) {
   }
 }
 
+// The same two roundings, kept apart: left to itself the compiler folds (float) and the 16-bit
+// conversion of f64_to_img into ONE float64 -> 16-bit rounding for some elements of an unrolled
+// loop and not for others (they differ at a 16-bit tie that only the float rounding creates, a
+// few elements per 10^5), so two kernels with the same source need not agree bit for bit. The
+// catalog image is written by two kernels that must (screen_image_kernel at load,
+// catalog_update_kernel for a live update): both use this form, which is also torch's
+// .float().to(f16 / bf16).
+template <int IMG>
+__device__ __forceinline__ uint16_t f64_to_img_rt(double v) {
+  float f = (float)v;
+  asm("" : "+v"(f));
+  if constexpr (IMG == EBT_F16) {
+    _Float16 h = (_Float16)f;
+    return __builtin_bit_cast(uint16_t, h);
+  } else {
+    __bf16 b = (__bf16)f;
+    return __builtin_bit_cast(uint16_t, b);
+  }
+}
+
 // ---- order-preserving float keys (0 = invalid: NaN or -inf) ---------------------------------
 __device__ __forceinline__ uint32_t f2key(float f) {
   uint32_t u = __float_as_uint(f);

@@ -409,6 +409,10 @@ bool valid_catalog(const ebt_catalog* c) {
 
 int screen_image(const void*, int, int64_t, int32_t, int64_t, const double*, int, int, void*,
                  int32_t, hipStream_t, unsigned int* err_max);
+int catalog_update(void* data, int dtype, int32_t d, int64_t ld, const int64_t* rows,
+                   int64_t row_offset, int64_t row0, int64_t m, const void* src, int src_dtype,
+                   int64_t ld_src, double* gnorm, float* inv32, void* img, int img_dtype,
+                   int32_t ld_img, int normalize, unsigned int* err_max, hipStream_t st);
 int64_t shard_lead_tiles(int64_t B_pad, int64_t n_rows, int64_t sample_tiles);
 int64_t shard_lead_room(int64_t B_pad, int64_t n_rows, int64_t sample_tiles);
 
@@ -429,17 +433,19 @@ size_t ebt_catalog_state_bytes(const void* data, int dtype, int64_t n, int32_t d
   return o;
 }
 
-int ebt_catalog_init(ebt_catalog* cat, const void* data, int dtype, int64_t n, int32_t d,
-                     int64_t ld, int64_t row_offset, void* state, size_t state_bytes,
-                     void* stream) {
-  const size_t need = ebt_catalog_state_bytes(data, dtype, n, d, ld);
-  if (!cat || !data || !state || need == 0 || row_offset < 0) {
-    set_error("ebt_catalog_init: bad arguments (n=%lld d=%d ld=%lld dtype=%d)", (long long)n, d,
-              (long long)ld, dtype);
+// ebt_catalog_init (n_cap == n) and ebt_catalog_init_reserved: the state is laid out for n_cap
+// rows and initialised for the first n
+static int catalog_init_cap(const char* who, ebt_catalog* cat, const void* data, int dtype,
+                            int64_t n, int64_t n_cap, int32_t d, int64_t ld, int64_t row_offset,
+                            void* state, size_t state_bytes, void* stream) {
+  const size_t need = n_cap >= n ? ebt_catalog_state_bytes(data, dtype, n_cap, d, ld) : 0;
+  if (!cat || !data || !state || need == 0 || n < 1 || row_offset < 0) {
+    set_error("%s: bad arguments (n=%lld n_cap=%lld d=%d ld=%lld dtype=%d)", who, (long long)n,
+              (long long)n_cap, d, (long long)ld, dtype);
     return EBT_EINVAL;
   }
   if (state_bytes < need) {
-    set_error("ebt_catalog_init: state %zu < %zu bytes", state_bytes, need);
+    set_error("%s: state %zu < %zu bytes", who, state_bytes, need);
     return EBT_ENOMEM;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -453,15 +459,15 @@ int ebt_catalog_init(ebt_catalog* cat, const void* data, int dtype, int64_t n, i
   c.d_pad = (int32_t)round_up(d, 64);
   char* s = (char*)state;
   c.gnorm64 = (double*)s;
-  c.inv32 = (float*)(s + al((size_t)n * 8));
-  char* img = s + al((size_t)n * 8) + al((size_t)round_up(n, 128) * 4);
+  c.inv32 = (float*)(s + al((size_t)n_cap * 8));
+  char* img = s + al((size_t)n_cap * 8) + al((size_t)round_up(n_cap, 128) * 4);
   const float one = 1.0f;
   uint32_t one_bits;
   memcpy(&one_bits, &one, 4);
   int rc = EBT_OK;
-  if (round_up(n, 128) > n)
+  if (round_up(n_cap, 128) > n)
     rc = hip_check(hipMemsetD32Async((hipDeviceptr_t)(c.inv32 + n), (int)one_bits,
-                                     (size_t)(round_up(n, 128) - n), st), "hipMemsetD32Async");
+                                     (size_t)(round_up(n_cap, 128) - n), st), "hipMemsetD32Async");
   if (!rc) rc = ebt_row_norms(data, dtype, n, d, ld, c.gnorm64, c.inv32, st);
   if (rc) return rc;
   const bool native = dtype == EBT_F16 || dtype == EBT_BF16;
@@ -489,7 +495,7 @@ int ebt_catalog_init(ebt_catalog* cat, const void* data, int dtype, int64_t n, i
     c.native = 0;
     c.ld_img = c.d_pad;
     c.image = img;
-    unsigned int* d_err = (unsigned int*)(img + al((size_t)n * c.d_pad * 2));
+    unsigned int* d_err = (unsigned int*)(img + al((size_t)n_cap * c.d_pad * 2));
     unsigned int h_err = 0;
     rc = hip_check(hipMemsetAsync(d_err, 0, 4, st), "hipMemsetAsync");
     if (!rc)
@@ -506,6 +512,155 @@ int ebt_catalog_init(ebt_catalog* cat, const void* data, int dtype, int64_t n, i
   }
   if (rc) return rc;
   *cat = c;
+  return EBT_OK;
+}
+
+int ebt_catalog_init(ebt_catalog* cat, const void* data, int dtype, int64_t n, int32_t d,
+                     int64_t ld, int64_t row_offset, void* state, size_t state_bytes,
+                     void* stream) {
+  return catalog_init_cap("ebt_catalog_init", cat, data, dtype, n, n, d, ld, row_offset, state,
+                          state_bytes, stream);
+}
+
+int ebt_catalog_init_reserved(ebt_catalog* cat, const void* data, int dtype, int64_t n,
+                              int64_t n_cap, int32_t d, int64_t ld, int64_t row_offset,
+                              void* state, size_t state_bytes, void* stream) {
+  return catalog_init_cap("ebt_catalog_init_reserved", cat, data, dtype, n, n_cap, d, ld,
+                          row_offset, state, state_bytes, stream);
+}
+
+// ---- live updates (0.4.0): catalog_update.hip ------------------------------------------------
+size_t ebt_catalog_update_bytes(int64_t m) { return m > 0 ? al((size_t)m * 8) : 0; }
+
+namespace {
+
+// Where catalog_init_cap put the parts of a state laid out for n_cap rows
+struct StateParts {
+  double* gnorm;
+  float* inv32;
+  void* img;              // NULL: the matrix is its own image
+  unsigned int* err;      // NULL for a native catalog
+};
+
+// Host checks shared by the two update entries: *cat is a catalog that catalog_init_cap laid out
+// in `state` for n_cap rows, and the source is usable
+int update_check(const char* who, const ebt_catalog* cat, void* state, size_t state_bytes,
+                 int64_t n_cap, int64_t m, const void* src, int src_dtype, int64_t ld_src,
+                 StateParts* out) {
+  if (!valid_catalog(cat) || !state || cat->dtype < 0 || cat->dtype > 3 || cat->row_offset < 0) {
+    set_error("%s: bad catalog or state", who);
+    return EBT_EINVAL;
+  }
+  const ebt_catalog& c = *cat;
+  if (m < 0 || src_dtype < 0 || src_dtype > 3 || (m > 0 && (!src || ld_src < c.d))) {
+    set_error("%s: bad source (m=%lld src_dtype=%d ld_src=%lld d=%d)", who, (long long)m,
+              src_dtype, (long long)ld_src, c.d);
+    return EBT_EINVAL;
+  }
+  const size_t need = n_cap >= c.n ? ebt_catalog_state_bytes(c.data, c.dtype, n_cap, c.d, c.ld) : 0;
+  if (need == 0 || state_bytes < need) {
+    set_error("%s: n_cap %lld (n %lld) needs a state of %zu bytes, got %zu", who,
+              (long long)n_cap, (long long)c.n, need, state_bytes);
+    return EBT_EINVAL;
+  }
+  const bool native = c.dtype == EBT_F16 || c.dtype == EBT_BF16;
+  const bool alias = native && c.d % 64 == 0 && c.ld % 64 == 0 && ((uintptr_t)c.data & 15) == 0;
+  char* s = (char*)state;
+  StateParts P;
+  P.gnorm = (double*)s;
+  P.inv32 = (float*)(s + al((size_t)n_cap * 8));
+  char* img = s + al((size_t)n_cap * 8) + al((size_t)round_up(n_cap, 128) * 4);
+  P.img = alias ? nullptr : img;
+  P.err = native ? nullptr : (unsigned int*)(img + al((size_t)n_cap * c.d_pad * 2));
+  const void* want_image = alias ? c.data : (const void*)img;
+  const int32_t want_ld_img = alias ? (int32_t)c.ld : c.d_pad;
+  const int want_img_dtype = native ? c.dtype : EBT_F16;
+  if (c.gnorm64 != P.gnorm || c.inv32 != P.inv32 || c.image != want_image ||
+      c.ld_img != want_ld_img || c.img_dtype != want_img_dtype || c.native != (native ? 1 : 0) ||
+      c.cscale != (native ? P.inv32 : nullptr) || c.d_pad != (int32_t)round_up(c.d, 64)) {
+    set_error("%s: the catalog is not laid out in this state for n_cap = %lld (a catalog of "
+              "ebt_catalog_init / _reserved with the same capacity is required)", who,
+              (long long)n_cap);
+    return EBT_EINVAL;
+  }
+  *out = P;
+  return EBT_OK;
+}
+
+// the kernel, then for a non-native catalog the error slot read back into cat->u_cat
+int update_launch(ebt_catalog* cat, const StateParts& P, const int64_t* d_rows, int64_t row0,
+                  int64_t m, const void* src, int src_dtype, int64_t ld_src, hipStream_t st) {
+  const ebt_catalog& c = *cat;
+  int rc = catalog_update(const_cast<void*>(c.data), c.dtype, c.d, c.ld, d_rows, c.row_offset,
+                          row0, m, src, src_dtype, ld_src, P.gnorm, P.inv32, P.img, c.img_dtype,
+                          c.ld_img, c.native ? 0 : 1, P.err, st);
+  if (rc || !P.err) return rc;
+  unsigned int h_err = 0;
+  rc = hip_check(hipMemcpyAsync(&h_err, P.err, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  if (!rc) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (rc) return rc;
+  float u;
+  memcpy(&u, &h_err, 4);
+  cat->u_cat = std::isfinite(u) && u >= 0.0f ? u : 1.0f / 2048.0f;
+  return EBT_OK;
+}
+
+}  // namespace
+
+int ebt_catalog_update_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
+                            const int64_t* rows, int64_t m, const void* src, int src_dtype,
+                            int64_t ld_src, void* ws, size_t ws_bytes, void* stream) {
+  StateParts P;
+  int rc = update_check("ebt_catalog_update_rows", cat, state, state_bytes, n_cap, m, src,
+                        src_dtype, ld_src, &P);
+  if (rc) return rc;
+  if (m == 0) return EBT_OK;
+  const ebt_catalog& c = *cat;
+  if (!rows) {
+    set_error("ebt_catalog_update_rows: rows is NULL");
+    return EBT_EINVAL;
+  }
+  for (int64_t i = 0; i < m; ++i) {
+    if (rows[i] < c.row_offset || rows[i] >= c.row_offset + c.n) {
+      set_error("ebt_catalog_update_rows: rows[%lld] = %lld is not in [%lld, %lld)", (long long)i,
+                (long long)rows[i], (long long)c.row_offset, (long long)(c.row_offset + c.n));
+      return EBT_EINVAL;
+    }
+    if (i > 0 && rows[i] <= rows[i - 1]) {
+      set_error("ebt_catalog_update_rows: rows must be strictly ascending (rows[%lld] = %lld "
+                "after %lld)", (long long)i, (long long)rows[i], (long long)rows[i - 1]);
+      return EBT_EINVAL;
+    }
+  }
+  const size_t need = ebt_catalog_update_bytes(m);
+  if (!ws || ws_bytes < need) {
+    set_error("ebt_catalog_update_rows: workspace %zu < %zu bytes", ws ? ws_bytes : (size_t)0,
+              need);
+    return EBT_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  rc = hip_check(hipMemcpyAsync(ws, rows, (size_t)m * 8, hipMemcpyHostToDevice, st),
+                 "hipMemcpyAsync");
+  if (rc) return rc;
+  return update_launch(cat, P, (const int64_t*)ws, 0, m, src, src_dtype, ld_src, st);
+}
+
+int ebt_catalog_append_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
+                            int64_t m, const void* src, int src_dtype, int64_t ld_src,
+                            void* stream) {
+  StateParts P;
+  int rc = update_check("ebt_catalog_append_rows", cat, state, state_bytes, n_cap, m, src,
+                        src_dtype, ld_src, &P);
+  if (rc) return rc;
+  if (m > n_cap - cat->n) {
+    set_error("ebt_catalog_append_rows: n %lld + m %lld > n_cap %lld", (long long)cat->n,
+              (long long)m, (long long)n_cap);
+    return EBT_EINVAL;
+  }
+  if (m == 0) return EBT_OK;
+  rc = update_launch(cat, P, nullptr, cat->n, m, src, src_dtype, ld_src, (hipStream_t)stream);
+  if (rc) return rc;
+  cat->n += m;
   return EBT_OK;
 }
 

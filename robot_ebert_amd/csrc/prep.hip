@@ -95,7 +95,8 @@ int row_norms(const void* x, int dtype, int64_t n, int32_t d, int64_t ld, double
 // One wave per row (grid-stride over rows): the row's scale 1/gnorm is computed once per lane,
 // lanes take consecutive 16-byte output chunks (coalesced loads and stores), and with VEC the 8
 // source elements of a chunk come in 16-byte vector loads (one for 16-bit sources, two for f32,
-// four for f64). Same arithmetic as the element form: round_to(img, x * (1/gnorm)) in float64.
+// four for f64). Same arithmetic as the element form: round_to(img, x * (1/gnorm)) in float64,
+// rounded through float (f64_to_img_rt: bit for bit what catalog_update_kernel writes).
 template <int DT>
 __device__ __forceinline__ void load8_f64(const void* __restrict__ x, int64_t off, double (&v)[8]) {
   if constexpr (DT == EBT_F32) {
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(256) void screen_image_kernel(const void* __restric
           if (c * 8 + 8 <= d) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-              o[e] = f64_to_img<IMG>(v[u][e] * s);
+              o[e] = f64_to_img_rt<IMG>(v[u][e] * s);
               if (err_max) es += sq_err<IMG>(o[e], v[u][e] * s);
             }
           } else {
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(256) void screen_image_kernel(const void* __restric
             for (int e = 0; e < 8; ++e) {
               const int jj = c * 8 + e;
               const double w = jj < d ? load_as_f64<DT>(x, row * ld + jj) * s : 0.0;
-              o[e] = f64_to_img<IMG>(w);
+              o[e] = f64_to_img_rt<IMG>(w);
               if (err_max) es += sq_err<IMG>(o[e], w);
             }
           }
@@ -181,7 +182,7 @@ __global__ __launch_bounds__(256) void screen_image_kernel(const void* __restric
           for (int e = 0; e < 8; ++e) {
             const int jj = c * 8 + e;
             const double w = jj < d ? load_as_f64<DT>(x, row * ld + jj) * s : 0.0;
-            o[e] = f64_to_img<IMG>(w);
+            o[e] = f64_to_img_rt<IMG>(w);
             if (err_max) es += sq_err<IMG>(o[e], w);
           }
           *(u16x8_t*)(img + row * ld_img + c * 8) = o;

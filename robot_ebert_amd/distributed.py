@@ -75,6 +75,24 @@ def split_liked(liked: Sequence[Sequence[int]], begin: int, end: int):
     return local, counts
 
 
+def split_update(rows: Sequence[int], vectors, catalog):
+    """The part of a global update that this shard owns: (rows, vectors) restricted to the
+    GLOBAL rows in [catalog.row_offset, catalog.row_offset + catalog.n), in their given order.
+    Every rank can be handed the same update; ``catalog.update_rows(*split_update(...))`` then
+    applies its own rows (``catalog`` may be anything with ``row_offset`` and ``n``)."""
+    rows = [int(r) for r in rows]
+    if len(rows) != len(vectors):
+        raise EbertError(f"{len(vectors)} vectors for {len(rows)} rows")
+    lo = int(catalog.row_offset)
+    hi = lo + int(catalog.n)
+    keep = [i for i, r in enumerate(rows) if lo <= r < hi]
+    if isinstance(vectors, torch.Tensor):
+        sub = vectors[torch.tensor(keep, dtype=torch.int64, device=vectors.device)]
+    else:
+        sub = vectors[keep]
+    return [rows[i] for i in keep], sub
+
+
 class TorchCollectives:
     """The three collectives the two-phase path uses, over a torch.distributed group (RCCL on
     MI355X: backend "nccl"; gloo on CPU)."""
