@@ -638,7 +638,8 @@ int ebt_cosine_topk_sharded(const ebt_catalog* cat, const ebt_comm* comm, const 
  * row is in [row_offset, row_offset + n_rows) and whose approx is >= approx[k-1] - 2 eps, 0.0
  * for the rest; an all-reduce (SUM) of `exact` completes it; ebt_finalize_topk sorts the
  * candidates above the cut by (exact desc, row asc) into out_scores/out_rows [B][k] and
- * certifies like ebt_rescore (ovf = the all-reduced (MAX) overflow flags -> certified -1). */
+ * certifies like ebt_rescore (ovf = the all-reduced (MAX) overflow flags -> certified -1; a
+ * candidate row >= n_rows_global is no candidate and gives certified -2, which wins over -1). */
 int ebt_cosine_screen(const double* q64, const void* qimg, const float* qscale, const float* eps,
                       int64_t B, int64_t B_pad, const void* cat, int dtype, int64_t ld,
                       const double* gnorm64, const void* cimg, const float* cscale, int img_dtype,

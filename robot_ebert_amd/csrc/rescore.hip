@@ -1799,21 +1799,29 @@ __global__ __launch_bounds__(RTHREADS) void finalize_topk_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* sc = (double*)smem;
   int64_t* rw = (int64_t*)(sc + kpp);
-  __shared__ int nvalid;
+  __shared__ int nvalid, corrupt;
   const int tid = threadIdx.x;
   const int64_t b = blockIdx.x;
-  if (tid == 0) nvalid = 0;
+  if (tid == 0) {
+    nvalid = 0;
+    corrupt = 0;
+  }
   __syncthreads();
   const float* cv = cand_vals + b * kprime;
   const double cut = (double)cv[k - 1] - 2.0 * (double)eps[b];
   int myvalid = 0;
   for (int c = tid; c < kpp; c += RTHREADS) {
     const int64_t r = c < kprime ? cand_rows[b * kprime + c] : -1;
-    if (r >= 0) {
+    if (r >= n_rows) {  // corrupt entry (as rescore_kernel): not a candidate, certified = -2
+      corrupt = 1;
+      sc[c] = -__builtin_inf();
+      rw[c] = INT64_MAX;
+    } else if (r >= 0) {
       ++myvalid;
       const double v = exact[b * kprime + c];
-      sc[c] = ((double)cv[c] < cut || !(v == v)) ? -__builtin_inf() : v;
-      rw[c] = r;
+      const bool below = (double)cv[c] < cut;  // not a candidate: never fills an empty slot
+      sc[c] = (below || !(v == v)) ? -__builtin_inf() : v;
+      rw[c] = below ? INT64_MAX : r;
     } else {
       sc[c] = -__builtin_inf();
       rw[c] = INT64_MAX;
@@ -1837,6 +1845,7 @@ __global__ __launch_bounds__(RTHREADS) void finalize_topk_kernel(
     if (nvalid >= kprime && n_rows > kprime)
       ok = (double)cv[kprime - 1] < (double)cv[k - 1] - 2.0 * (double)eps[b];
     if (ovf && ovf[b]) ok = -1;
+    if (corrupt) ok = -2;  // internal error: row out of range
     certified[b] = ok;
   }
 }
