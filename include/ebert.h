@@ -73,7 +73,9 @@ extern "C" {
  *        ebt_merge_packed also flags a query with more than min(R k, 2 k + 256) entries.
  * 0.4.0: live catalog updates: ebt_catalog_init_reserved, ebt_catalog_update_bytes,
  *        ebt_catalog_update_rows, ebt_catalog_append_rows (additive; struct ebt_catalog and
- *        ebt_catalog_init are unchanged). */
+ *        ebt_catalog_init are unchanged).
+ * 0.5.0: rows removed in place: ebt_catalog_remove_bytes, ebt_catalog_remove_plan,
+ *        ebt_catalog_remove_rows (additive). */
 int ebt_version(void);
 
 /* Message for the last non-zero return on this thread ("" if none). */
@@ -377,7 +379,7 @@ int ebt_cosine_topk_prepared(const double* q64, const void* qimg, const float* q
  * device matrix and a caller-provided device STATE buffer of ebt_catalog_state_bytes() bytes
  * (float64 guarded row norms, float32 inverse norms, and the f16 screening image unless the
  * matrix itself is the MFMA operand: f16 / bf16 with d, ld % 64 == 0). Afterwards it changes
- * only through the live-update entries below (0.4.0), which rewrite rows and their state in place;
+ * only through the live-update entries below (0.4.0, 0.5.0), which rewrite rows and their state in place;
  * the struct and the state buffer must outlive every call that uses them. For a non-native
  * catalog (f32 / f64) ebt_catalog_init waits for `stream` once, to read back u_cat, the largest
  * row error of the image its kernel measured (0.3.1); a native catalog's init stays asynchronous. */
@@ -448,6 +450,49 @@ int ebt_catalog_update_rows(ebt_catalog* cat, void* state, size_t state_bytes, i
  * too small afterwards: size them again (or for n_cap from the start). */
 int ebt_catalog_append_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
                             int64_t m, const void* src, int src_dtype, int64_t ld_src,
+                            void* stream);
+
+/* ---- removal (0.5.0): remove rows in place --------------------------------------------------
+ * Removing m distinct rows from a catalog of n rows leaves n' = n - m rows. The holes H are the
+ * removed rows below n', ascending; the survivors S are the rows of [n', n) that are not removed,
+ * ascending. |H| = |S| = p, row S[i] moves to row H[i], and every other surviving row keeps its
+ * number (numpy: c2 = c.copy(); c2[H] = c[S]; c2 = c2[:n']). Sources are all >= n' and
+ * destinations all < n', so no move reads what another writes.
+ *
+ * Device scratch of ebt_catalog_remove_rows for m rows: round_up(16 m, 256) bytes (0 for
+ * m <= 0). */
+size_t ebt_catalog_remove_bytes(int64_t m);
+
+/* The moves of that rule, on the host (no GPU call). rows: m GLOBAL rows, strictly ascending, all
+ * in [row_offset, row_offset + n). from / to: room for m entries each; they receive the p moves
+ * as GLOBAL rows (from[i] -> to[i]); both may be NULL. Returns p, or -1 (ebt_last_error) on bad
+ * arguments, m >= n included. A caller that keeps row numbers (ratings stored as rows) remaps
+ * them with these pairs and drops the removed ones. */
+int64_t ebt_catalog_remove_plan(int64_t n, int64_t row_offset, const int64_t* rows, int64_t m,
+                                int64_t* from, int64_t* to);
+
+/* Remove m rows by exactly that plan: one copy of the (src, dst) pairs into ws, ONE kernel that
+ * copies for each move the d elements of the matrix row (columns d .. ld of `data` are not
+ * touched), the image row, gnorm64 and inv32, then inv32[n' .. n) = 1.0f again and cat->n -= m.
+ * Nothing is recomputed -- a row's norm and image row depend on its values and on catalog-wide
+ * alignment only -- so data, gnorm64, inv32 and the image are bit-identical to those of a catalog
+ * initialised from the edited matrix. Only tail rows removed (p == 0): no kernel runs.
+ *   cat, state, state_bytes, n_cap: as for ebt_catalog_update_rows.
+ *   rows: HOST pointer, m GLOBAL row ids, strictly ascending, all in [row_offset, row_offset + n).
+ *   ws: device scratch of ebt_catalog_remove_bytes(m) bytes.
+ * Every check (NULL rows, their order and range, m >= n: "cannot remove every row", the
+ * workspace size) runs on the host before any GPU call; a failed check returns EBT_EINVAL and
+ * leaves *cat and the device state unchanged. m == 0 is EBT_OK and does nothing.
+ * u_cat is not touched: the error slot is a running maximum and stays a valid bound, as after
+ * ebt_catalog_update_rows; there is no read-back, so for every catalog kind the call is as
+ * asynchronous as a native catalog's update (its only host-to-device traffic is the pair list).
+ * Ordering: as for the update entries, a removal is stream-ordered, and a batch whose _finish has
+ * not returned must be finished before it is issued. Row numbers change: exclusion and liked
+ * lists built before the removal must be remapped (ebt_catalog_remove_plan). Workspaces sized by
+ * ebt_workspace_bytes for the old n should be sized again. The rows n' .. n of `data` and of the
+ * state are free for ebt_catalog_append_rows. */
+int ebt_catalog_remove_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
+                            const int64_t* rows, int64_t m, void* ws, size_t ws_bytes,
                             void* stream);
 
 /* Optional knobs (NULL = defaults; a zero field = its default): kprime = the screen's candidate

@@ -5,8 +5,10 @@ hand-written HIP kernels for gfx950 behind the C ABI of include/ebert.h (libeber
 ctypes). Python keeps the reference's call surface: ``lib.get_user_recs`` and friends.
 
 The resident ``Catalog`` is live: ``Catalog.update_rows`` / ``Catalog.append`` (ABI 0.4.0) replace
-and append rows in place; ``RecBatcher.update_rows`` / ``.append`` do so between batches and
-``distributed.split_update`` hands each shard of a row-sharded catalog its part of an update.
+and append rows in place, and ``Catalog.remove`` (ABI 0.5.0) removes rows in place, filling the
+holes from the tail and returning the moves ``(old_row, new_row)``; ``RecBatcher.update_rows`` /
+``.append`` / ``.remove`` do so between batches and ``distributed.split_update`` hands each shard
+of a row-sharded catalog its part of an update.
 """
 from ._lib import EbertError, Timer, load  # noqa: F401
 from .catalog import Catalog  # noqa: F401

@@ -92,6 +92,9 @@ _SIGNATURES = {
     "ebt_catalog_update_rows": ([_PCAT, _VP, _SZ, _I64, _VP, _I64, _VP, _INT, _I64, _VP, _SZ, _VP],
                                 _INT),
     "ebt_catalog_append_rows": ([_PCAT, _VP, _SZ, _I64, _I64, _VP, _INT, _I64, _VP], _INT),
+    "ebt_catalog_remove_bytes": ([_I64], _SZ),
+    "ebt_catalog_remove_plan": ([_I64, _I64, _VP, _I64, _VP, _VP], _I64),
+    "ebt_catalog_remove_rows": ([_PCAT, _VP, _SZ, _I64, _VP, _I64, _VP, _SZ, _VP], _INT),
     "ebt_workspace_bytes": ([_PCAT, _I64, _I32, _POPT], _SZ),
     "ebt_cosine_topk": ([_PCAT, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP, _POPT, _VP, _SZ,
                          _VP, _VP, _VP, _VP], _INT),

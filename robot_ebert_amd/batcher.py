@@ -22,7 +22,7 @@ concurrently, SURVEY §8b "Threading") only the dispatcher does.
 * Bounded statistics: ``batches`` keeps the sizes of the last ``history`` batches; ``stats()``
   gives totals and a power-of-two batch-size histogram.
 
-* Live updates: ``update_rows`` / ``append`` hand a catalog edit to the dispatcher, which treats it
+* Live updates: ``update_rows`` / ``append`` / ``remove`` hand a catalog edit to the dispatcher, which treats it
   as a barrier: everything queued before it is dispatched, every in-flight batch is finished,
   the edit is applied, then collection resumes (ebert.h: an update must not overtake a batch
   whose finish has not returned).
@@ -184,6 +184,14 @@ class RecBatcher:
         """``catalog.append(vectors, ids)`` under the same barrier; requests submitted after
         the Future resolves are validated against the new n."""
         return self._edit("append", (vectors, ids))
+
+    def remove(self, rows_or_ids) -> Future:
+        """``catalog.remove(rows_or_ids)`` under the same barrier: requests queued before this
+        call are scored against the old catalog; the Future resolves to the moves
+        ``[(old_row, new_row), ...]`` (or the removal's error), and requests submitted after that
+        are validated against the new n. Row numbers a caller holds must be remapped by the moves
+        before they are submitted again."""
+        return self._edit("remove", (rows_or_ids,))
 
     def _edit(self, method: str, args: tuple) -> Future:
         fut: Future = Future()

@@ -20,7 +20,7 @@ screening").
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Iterable, List, Optional, Sequence
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -128,7 +128,7 @@ class Catalog:
             self.image = self.state[off_img:off_img + self.n * self.ld_img * 2].view(
                 self.img_torch_dtype).view(self.n, self.ld_img)
 
-    # ---- live updates (ebt_catalog_update_rows / ebt_catalog_append_rows) -----------------
+    # ---- live updates (ebt_catalog_update_rows / _append_rows / _remove_rows) --------------
     def _vectors(self, vectors, m: Optional[int]) -> torch.Tensor:
         """The update's source rows as a device tensor [m, d] of a supported dtype, checked."""
         if self.state is None:
@@ -225,6 +225,68 @@ class Catalog:
             self.ids.extend(ids)
             for i, t in enumerate(ids):
                 self._pos[t] = first + i
+
+    def remove(self, rows_or_ids) -> List[Tuple[int, int]]:
+        """Remove rows in place: ``rows_or_ids`` are GLOBAL rows or string ids, in any order.
+        With n' = n - m, the removed rows below n' are filled, in ascending order, with the rows
+        of [n', n) that are not removed, in ascending order (include/ebert.h, "removal"); every
+        other row keeps its number. Returns those moves as ``(old_row, new_row)`` pairs, for a
+        caller that holds row numbers to remap them. One kernel copies the moved rows with their
+        norms and image rows; the state afterwards equals that of a catalog built from the edited
+        matrix (``u_cat`` is kept). n, n_global, the ids and the id -> row map follow, and the
+        freed rows are available to ``append``. Refused on a row-sharded catalog. Ordering as
+        for ``update_rows``. Bad arguments raise EbertError before any GPU work and leave the
+        catalog unchanged."""
+        if self.state is None:
+            raise EbertError("a from_parts catalog cannot be edited: its norms and image are "
+                             "the caller's tensors, not a state this library laid out")
+        if self.row_offset != 0 or self.n_global != self.n:
+            raise EbertError("remove on a row-sharded catalog is not supported")
+        items = list(rows_or_ids)
+        if any(isinstance(t, str) for t in items):
+            try:
+                rows = self.rows_of(items)
+            except KeyError as e:
+                raise EbertError(f"unknown id {e}") from e
+        else:
+            try:
+                rows = [int(r) for r in items]
+            except (TypeError, ValueError) as e:
+                raise EbertError(f"malformed rows: {e}") from e
+        for r in rows:
+            if r < 0 or r >= self.n:
+                raise EbertError(f"row {r} is not in the catalog rows [0, {self.n})")
+        if len(set(rows)) != len(rows):
+            raise EbertError("duplicate rows in one removal")
+        m = len(rows)
+        if m >= self.n:
+            raise EbertError(f"cannot remove every row ({m} of {self.n})")
+        if m == 0:
+            return []
+        host_rows = np.asarray(sorted(rows), dtype=np.int64)
+        src, dst = np.empty(m, dtype=np.int64), np.empty(m, dtype=np.int64)
+        lib = _lib.load()
+        p = lib.ebt_catalog_remove_plan(self.n, 0, host_rows.ctypes.data, m, src.ctypes.data,
+                                        dst.ctypes.data)
+        if p < 0:
+            raise EbertError("ebt_catalog_remove_plan failed: " +
+                             lib.ebt_last_error().decode(errors="replace"))
+        moves = [(int(s), int(t)) for s, t in zip(src[:p], dst[:p])]
+        ws = torch.empty(lib.ebt_catalog_remove_bytes(m), dtype=torch.uint8, device=self.device)
+        call("ebt_catalog_remove_rows", ctypes.byref(self.cstruct), ptr(self.state),
+             self.state.numel(), self.capacity, host_rows.ctypes.data, m, ptr(ws), ws.numel(),
+             stream_of(self.device))
+        self._views()
+        self.n_global = self.n
+        if self.ids is not None:
+            pos = self.index_pos
+            for r in rows:
+                del pos[self.ids[r]]
+            for s, t in moves:
+                self.ids[t] = self.ids[s]
+                pos[self.ids[t]] = t
+            del self.ids[self.n:]
+        return moves
 
     # ---- constructors ---------------------------------------------------------------------
     @classmethod

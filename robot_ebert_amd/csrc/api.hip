@@ -701,7 +701,7 @@ using namespace ebt;
 
 extern "C" {
 
-int ebt_version(void) { return 400; }  // 0.4.0: live catalog updates (ebert.h)
+int ebt_version(void) { return 500; }  // 0.5.0: catalog rows removed in place (ebert.h)
 
 const char* ebt_last_error(void) { return g_err; }
 

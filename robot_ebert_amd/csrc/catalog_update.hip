@@ -23,6 +23,16 @@
 // order of operations, one more pass over the row through L2).
 //
 // A NaN's payload is not kept by the conversion (it stays a NaN), also between equal dtypes.
+//
+// Removal (ebert.h 0.5.0: ebt_catalog_remove_rows): catalog_move_kernel, one wave per move
+// (src, dst) of ebt_catalog_remove_plan, four waves per block, grid-stride over the p moves; no
+// LDS, no barriers, no atomics. A wave copies the d elements of data[src] to data[dst] (the
+// columns d .. ld are the caller's), the image row (unless the matrix is its own image), and
+// gnorm64 / inv32. Nothing is recomputed: a row's norm and image row are functions of its values
+// and of catalog-wide alignment only, so the copies are what ebt_catalog_init computes for the
+// edited matrix. Every source is >= n' and every destination < n': no move reads what another
+// writes. The kernel is bound by memory latency: a lane issues the loads of up to MOVE_AHEAD
+// 16-byte chunks before their stores.
 #include "common.h"
 
 namespace ebt {
@@ -312,6 +322,89 @@ int catalog_update(void* data, int dtype, int32_t d, int64_t ld, const int64_t* 
 #undef EBT_UP
 #undef EBT_UP_V
   return launch_check("catalog_update_kernel");
+}
+
+// ---- removal: rows moved into the holes -------------------------------------------------------
+constexpr int MOVE_AHEAD = 4;   // 16-byte chunks a lane loads before it stores them
+
+struct MoveArgs {
+  void* data;              // the catalog matrix [.][ld]
+  int64_t ld;
+  int d;
+  const int64_t* moves;    // device, p pairs (src, dst) of LOCAL rows
+  int64_t p;
+  int64_t n_new, n_old;    // every src in [n_new, n_old), every dst in [0, n_new)
+  double* gnorm;
+  float* inv32;
+  uint16_t* img;           // NULL: the matrix is its own image
+  int ld_img;
+  int cat_vec;             // catalog rows 16-byte aligned
+};
+
+// nchunks 16-byte chunks from src to dst (both 16-byte aligned), MOVE_AHEAD loads in flight
+__device__ __forceinline__ void move_chunks(const u16x8_t* __restrict__ src,
+                                            u16x8_t* __restrict__ dst, int nchunks, int lane) {
+  for (int c = lane; c < nchunks; c += 64 * MOVE_AHEAD) {
+    u16x8_t v[MOVE_AHEAD];
+#pragma unroll
+    for (int u = 0; u < MOVE_AHEAD; ++u)
+      if (c + 64 * u < nchunks) v[u] = src[c + 64 * u];
+#pragma unroll
+    for (int u = 0; u < MOVE_AHEAD; ++u)
+      if (c + 64 * u < nchunks) dst[c + 64 * u] = v[u];
+  }
+}
+
+// T: an unsigned integer of the element's size (the bits are copied, a NaN's payload included)
+template <typename T>
+__global__ __launch_bounds__(256) void catalog_move_kernel(const MoveArgs a) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  constexpr int PER = 16 / (int)sizeof(T);   // elements per 16-byte chunk
+  for (int64_t i = (int64_t)blockIdx.x * 4 + w; i < a.p; i += (int64_t)gridDim.x * 4) {
+    const int64_t src = a.moves[2 * i], dst = a.moves[2 * i + 1];
+    // the host's plan keeps to these ranges; a pair outside them is never followed
+    if (src < a.n_new || src >= a.n_old || dst < 0 || dst >= a.n_new) continue;
+    const T* __restrict__ s = (const T*)a.data + src * a.ld;
+    T* __restrict__ t = (T*)a.data + dst * a.ld;
+    const int nvec = a.cat_vec ? a.d / PER : 0;
+    move_chunks((const u16x8_t*)s, (u16x8_t*)t, nvec, lane);
+    for (int j = nvec * PER + lane; j < a.d; j += 64) t[j] = s[j];
+    if (a.img)
+      move_chunks((const u16x8_t*)(a.img + src * a.ld_img), (u16x8_t*)(a.img + dst * a.ld_img),
+                  a.ld_img / 8, lane);
+    if (lane == 0) {
+      a.gnorm[dst] = a.gnorm[src];
+      a.inv32[dst] = a.inv32[src];
+    }
+  }
+}
+
+// Host side: every argument was checked by the caller (driver.hip); `moves` is a device array of
+// p (src, dst) pairs of LOCAL rows. img == NULL when the matrix is its own image.
+int catalog_move(void* data, int dtype, int32_t d, int64_t ld, const int64_t* moves, int64_t p,
+                 int64_t n_new, int64_t n_old, double* gnorm, float* inv32, void* img,
+                 int32_t ld_img, hipStream_t st) {
+  if (!data || !gnorm || !inv32 || p < 0 || (p > 0 && !moves) || d <= 0 || ld < d || dtype < 0 ||
+      dtype > 3 || n_new < 1 || n_old < n_new || p > n_old - n_new ||
+      (img && (ld_img < d || ld_img % 64 != 0 || ((uintptr_t)img & 15)))) {
+    set_error("catalog_move: bad arguments");
+    return EBT_EINVAL;
+  }
+  if (p == 0) return EBT_OK;
+  const int es = dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2);
+  MoveArgs a;
+  a.data = data; a.ld = ld; a.d = d; a.moves = moves; a.p = p; a.n_new = n_new; a.n_old = n_old;
+  a.gnorm = gnorm; a.inv32 = inv32; a.img = (uint16_t*)img; a.ld_img = ld_img;
+  a.cat_vec = ((uintptr_t)data & 15) == 0 && (ld * es) % 16 == 0;
+  int64_t blocks = ceil_div(p, 4);
+  if (blocks > 4096) blocks = 4096;
+  dim3 grid((unsigned)blocks), block(256);
+  switch (es) {
+    case 8: hipLaunchKernelGGL((catalog_move_kernel<uint64_t>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((catalog_move_kernel<uint32_t>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((catalog_move_kernel<uint16_t>), grid, block, 0, st, a); break;
+  }
+  return launch_check("catalog_move_kernel");
 }
 
 }  // namespace ebt

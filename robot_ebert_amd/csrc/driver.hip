@@ -413,6 +413,9 @@ int catalog_update(void* data, int dtype, int32_t d, int64_t ld, const int64_t* 
                    int64_t row_offset, int64_t row0, int64_t m, const void* src, int src_dtype,
                    int64_t ld_src, double* gnorm, float* inv32, void* img, int img_dtype,
                    int32_t ld_img, int normalize, unsigned int* err_max, hipStream_t st);
+int catalog_move(void* data, int dtype, int32_t d, int64_t ld, const int64_t* moves, int64_t p,
+                 int64_t n_new, int64_t n_old, double* gnorm, float* inv32, void* img,
+                 int32_t ld_img, hipStream_t st);
 int64_t shard_lead_tiles(int64_t B_pad, int64_t n_rows, int64_t sample_tiles);
 int64_t shard_lead_room(int64_t B_pad, int64_t n_rows, int64_t sample_tiles);
 
@@ -661,6 +664,111 @@ int ebt_catalog_append_rows(ebt_catalog* cat, void* state, size_t state_bytes, i
   rc = update_launch(cat, P, nullptr, cat->n, m, src, src_dtype, ld_src, (hipStream_t)stream);
   if (rc) return rc;
   cat->n += m;
+  return EBT_OK;
+}
+
+// ---- removal (0.5.0): catalog_update.hip catalog_move_kernel ----------------------------------
+size_t ebt_catalog_remove_bytes(int64_t m) { return m > 0 ? al((size_t)m * 16) : 0; }
+
+namespace {
+
+// The rule of ebert.h: with n' = n - m, the removed rows below n' (the holes, ascending) receive
+// the rows of [n', n) that are not removed (the survivors, ascending). `rows` is checked; the p
+// moves go to from / to (GLOBAL rows) when given. Returns p, or -1 with the error set.
+int64_t remove_plan(const char* who, int64_t n, int64_t row_offset, const int64_t* rows,
+                    int64_t m, int64_t* from, int64_t* to) {
+  if (n < 1 || row_offset < 0 || m < 0 || (m > 0 && !rows) || ((from == nullptr) != (to == nullptr))) {
+    set_error("%s: bad arguments (n=%lld row_offset=%lld m=%lld; from / to both or neither)", who,
+              (long long)n, (long long)row_offset, (long long)m);
+    return -1;
+  }
+  for (int64_t i = 0; i < m; ++i) {
+    if (rows[i] < row_offset || rows[i] >= row_offset + n) {
+      set_error("%s: rows[%lld] = %lld is not in [%lld, %lld)", who, (long long)i,
+                (long long)rows[i], (long long)row_offset, (long long)(row_offset + n));
+      return -1;
+    }
+    if (i > 0 && rows[i] <= rows[i - 1]) {
+      set_error("%s: rows must be strictly ascending (rows[%lld] = %lld after %lld)", who,
+                (long long)i, (long long)rows[i], (long long)rows[i - 1]);
+      return -1;
+    }
+  }
+  if (m >= n) {
+    set_error("%s: cannot remove every row (m %lld >= n %lld)", who, (long long)m, (long long)n);
+    return -1;
+  }
+  const int64_t n_new = n - m;
+  int64_t p = 0;
+  while (p < m && rows[p] - row_offset < n_new) ++p;   // the holes are rows[0 .. p)
+  // rows[p .. m) are the removed rows of [n', n): the survivors are the others, p of them
+  int64_t t = p, s = n_new;
+  for (int64_t i = 0; i < p; ++i, ++s) {
+    while (t < m && rows[t] - row_offset == s) ++t, ++s;
+    if (from) {
+      from[i] = row_offset + s;
+      to[i] = rows[i];
+    }
+  }
+  return p;
+}
+
+}  // namespace
+
+int64_t ebt_catalog_remove_plan(int64_t n, int64_t row_offset, const int64_t* rows, int64_t m,
+                                int64_t* from, int64_t* to) {
+  return remove_plan("ebt_catalog_remove_plan", n, row_offset, rows, m, from, to);
+}
+
+int ebt_catalog_remove_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
+                            const int64_t* rows, int64_t m, void* ws, size_t ws_bytes,
+                            void* stream) {
+  const char* who = "ebt_catalog_remove_rows";
+  StateParts P;
+  int rc = update_check(who, cat, state, state_bytes, n_cap, 0, nullptr, 0, 0, &P);
+  if (rc) return rc;
+  if (m < 0) {
+    set_error("%s: m = %lld", who, (long long)m);
+    return EBT_EINVAL;
+  }
+  if (m == 0) return EBT_OK;
+  if (!rows) {
+    set_error("%s: rows is NULL", who);
+    return EBT_EINVAL;
+  }
+  const ebt_catalog& c = *cat;
+  std::vector<int64_t> from((size_t)m), to((size_t)m);
+  const int64_t p = remove_plan(who, c.n, c.row_offset, rows, m, from.data(), to.data());
+  if (p < 0) return EBT_EINVAL;
+  const size_t need = ebt_catalog_remove_bytes(m);
+  if (!ws || ws_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", who, ws ? ws_bytes : (size_t)0, need);
+    return EBT_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n_new = c.n - m;
+  if (p > 0) {
+    std::vector<int64_t> pairs((size_t)p * 2);   // LOCAL (src, dst)
+    for (int64_t i = 0; i < p; ++i) {
+      pairs[2 * i] = from[i] - c.row_offset;
+      pairs[2 * i + 1] = to[i] - c.row_offset;
+    }
+    // a copy from pageable memory has left the host buffer when the call returns
+    rc = hip_check(hipMemcpyAsync(ws, pairs.data(), (size_t)p * 16, hipMemcpyHostToDevice, st),
+                   "hipMemcpyAsync");
+    if (!rc)
+      rc = catalog_move(const_cast<void*>(c.data), c.dtype, c.d, c.ld, (const int64_t*)ws, p,
+                        n_new, c.n, P.gnorm, P.inv32, P.img, c.ld_img, st);
+    if (rc) return rc;
+  }
+  // after the moves, which read inv32 in this range: rows past n' hold 1.0f again
+  const float one = 1.0f;
+  uint32_t one_bits;
+  memcpy(&one_bits, &one, 4);
+  rc = hip_check(hipMemsetD32Async((hipDeviceptr_t)(P.inv32 + n_new), (int)one_bits, (size_t)m, st),
+                 "hipMemsetD32Async");
+  if (rc) return rc;
+  cat->n = n_new;
   return EBT_OK;
 }
 
