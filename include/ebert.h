@@ -75,7 +75,12 @@ extern "C" {
  *        ebt_catalog_update_rows, ebt_catalog_append_rows (additive; struct ebt_catalog and
  *        ebt_catalog_init are unchanged).
  * 0.5.0: rows removed in place: ebt_catalog_remove_bytes, ebt_catalog_remove_plan,
- *        ebt_catalog_remove_rows (additive). */
+ *        ebt_catalog_remove_rows (additive).
+ * 0.6.0: per-query allow masks: ebt_allow, ebt_allow_words, ebt_allow_from_bool,
+ *        ebt_allow_set_rows, ebt_mask_allowed, ebt_cosine_topk_prepared_allowed,
+ *        ebt_cosine_topk_allowed / _allowed_submit / _allowed_finish (additive; no existing
+ *        struct or signature changes; ebt_workspace_bytes grows by the retry group's mask ids,
+ *        at most 1 KiB). */
 int ebt_version(void);
 
 /* Message for the last non-zero return on this thread ("" if none). */
@@ -567,6 +572,78 @@ int ebt_cosine_topk_submit(const ebt_catalog* cat, const void* q, int q_dtype, i
                            int64_t* out_rows, int32_t* cert_host, ebt_pending* pending,
                            void* timer, void* stream);
 int ebt_cosine_topk_finish(ebt_pending* pending);
+
+/* ---- per-query allow masks (0.6.0): top-k within a subset of the catalog rows --------------
+ * The reference's candidate set is index.difference(rated) (lib.py:48,55); here it is
+ * intersected with a set of allowed rows chosen per query ("within this genre", "only this
+ * tenant's items"): the result of a filtered query is the top k of (allowed rows minus excluded
+ * rows), same order, same GLOBAL row ids, same float64 scores, NaN / -1 past the candidates.
+ *
+ * An allow table is uint32 masks[n_masks][words] in device memory, 16-byte aligned, with
+ * words = ebt_allow_words(n_rows) = ceil(n_rows / 32) rounded up to a multiple of 4 (every mask
+ * row 16-byte aligned); n_rows is the catalog's capacity (n_global for a shard: bits are indexed
+ * by GLOBAL row). Row r is allowed in mask m iff masks[m * words + (r >> 5)] >> (r & 31) & 1;
+ * rows >= 32 * words are not allowed. mask_id is device int32 [B]: -1 (any negative value) = the
+ * query is unfiltered and its scores are not touched; an id >= n_masks masks every row of that
+ * query (all slots NaN / -1; nothing is read out of bounds). The result depends on the set of
+ * allowed rows only.
+ *
+ * ebt_allow_from_bool packs uint8 flags[n] (non-zero = allowed; device) into one mask row and
+ * zeroes the rest of its `words` words. ebt_allow_set_rows sets (allowed != 0) or clears the
+ * bits of the m GLOBAL rows of a device list in one mask row (atomics on the word: duplicates
+ * are fine; rows outside [0, 32 * words) are ignored). Both only enqueue on `stream`.
+ *
+ * ebt_mask_allowed: scores [B][ld_scores] f32 (16-byte aligned, ld_scores % 4 == 0) holds the
+ * scores of GLOBAL rows [col_begin, col_end), any col_begin >= 0; every disallowed entry of a
+ * filtered query becomes -inf, columns [col_end - col_begin, ld_scores) are left alone. It is
+ * the pass the pipeline runs right after ebt_mask_excluded on each score chunk of the unfused
+ * path (timed as EBT_STAGE_MASK). Host checks before any GPU call, EBT_EINVAL: NULL pointers,
+ * words < 1 or not a multiple of 4, n_masks < 1, 32 * words < col_end.
+ *
+ * The _allowed entries take their twin's arguments plus `allow`. allow == NULL: exactly the
+ * twin, fused screen included. Otherwise the batch runs the unfused path: the entries set
+ * EBT_FLAG_NO_FUSE themselves and the caller sizes the workspace with that flag
+ * (ebt_workspace_bytes / ebt_cosine_topk_workspace; EBT_ENOMEM when it is too small), and
+ * 32 * words must reach row_offset + n. The float64 screen (EBT_FLAG_EXACT) is filtered the same
+ * way. _finish takes the same ebt_allow again (ebt_pending, which callers allocate, does not
+ * grow): the table and mask_id stay valid and unchanged until it returns. min(k, n) > 4096 (the
+ * full-sort path) with a non-NULL allow is EBT_EUNSUPPORTED; ebt_cosine_topk_sharded takes no
+ * masks. */
+typedef struct ebt_allow {
+  const uint32_t* masks;    /* device [n_masks][words] */
+  int64_t words;            /* ebt_allow_words(capacity) */
+  int32_t n_masks;
+  const int32_t* mask_id;   /* device [B]: mask of query b, -1 = unfiltered */
+} ebt_allow;
+int64_t ebt_allow_words(int64_t n_rows);
+int ebt_allow_from_bool(const uint8_t* flags, int64_t n, uint32_t* mask_row, int64_t words,
+                        void* stream);
+int ebt_allow_set_rows(uint32_t* mask_row, int64_t words, const int64_t* rows, int64_t m,
+                       int allowed, void* stream);
+int ebt_mask_allowed(float* scores, int64_t ld_scores, int64_t B, int64_t col_begin,
+                     int64_t col_end, const ebt_allow* allow, void* stream);
+int ebt_cosine_topk_prepared_allowed(
+    const double* q64, const void* qimg, const float* qscale, const float* eps, int64_t B,
+    int64_t B_pad, const void* cat, int dtype, int64_t ld, const double* gnorm64,
+    const void* cimg, const float* cscale, int img_dtype, int32_t ld_img, int64_t n_rows,
+    int32_t d, int32_t d_pad, int64_t row_offset, const int64_t* excl_off,
+    const int64_t* excl_rows, int32_t k, int32_t kprime, int64_t chunk_rows, int flags,
+    void* workspace, size_t ws_bytes, double* out_scores, int64_t* out_rows, int32_t* certified,
+    void* timer, void* stream, const ebt_allow* allow);
+int ebt_cosine_topk_allowed(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                            int64_t ldq, const int64_t* liked_off, const int64_t* liked_rows,
+                            int32_t k, const int64_t* excl_off, const int64_t* excl_rows,
+                            const ebt_options* opt, void* workspace, size_t ws_bytes,
+                            double* out_scores, int64_t* out_rows, void* timer, void* stream,
+                            const ebt_allow* allow);
+int ebt_cosine_topk_allowed_submit(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                                   int64_t ldq, const int64_t* liked_off,
+                                   const int64_t* liked_rows, int32_t k, const int64_t* excl_off,
+                                   const int64_t* excl_rows, const ebt_options* opt,
+                                   void* workspace, size_t ws_bytes, double* out_scores,
+                                   int64_t* out_rows, int32_t* cert_host, ebt_pending* pending,
+                                   void* timer, void* stream, const ebt_allow* allow);
+int ebt_cosine_topk_allowed_finish(ebt_pending* pending, const ebt_allow* allow);
 
 /* ---- row-sharded catalog, self-contained: one call per batch on every rank ---------------
  * The per-shard protocol of robot_ebert_amd/distributed.py (score_topk_sharded_local_stages)

@@ -9,9 +9,13 @@ and append rows in place, and ``Catalog.remove`` (ABI 0.5.0) removes rows in pla
 holes from the tail and returning the moves ``(old_row, new_row)``; ``RecBatcher.update_rows`` /
 ``.append`` / ``.remove`` do so between batches and ``distributed.split_update`` hands each shard
 of a row-sharded catalog its part of an update.
+
+``AllowMasks`` (ABI 0.6.0) restricts a query to a subset of the rows: ``score_topk(..., allow=(masks,
+mask_ids))`` returns the top k of (allowed rows minus excluded rows).
 """
 from ._lib import EbertError, Timer, load  # noqa: F401
 from .catalog import Catalog  # noqa: F401
+from .allow import AllowMasks  # noqa: F401
 from .search import (merge_topk, prepare_queries, rescore_rows, score_topk,  # noqa: F401
                      score_topk_finish, score_topk_submit)
 from . import ops  # noqa: F401,E402  (registers torch.ops.ebert.*)

@@ -57,6 +57,11 @@ class EbtPending(ctypes.Structure):
                 ("event", _VP), ("timer", _VP), ("stream", _VP)]
 
 
+class EbtAllow(ctypes.Structure):
+    """include/ebert.h `ebt_allow`: the per-query allow masks of the _allowed entries."""
+    _fields_ = [("masks", _VP), ("words", _I64), ("n_masks", _I32), ("mask_id", _VP)]
+
+
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, _VP, _VP, _VP, _SZ, _VP)
 
 
@@ -81,6 +86,7 @@ class EbtShardedPending(ctypes.Structure):
 _PCAT, _POPT, _PPEND = (ctypes.POINTER(EbtCatalog), ctypes.POINTER(EbtOptions),
                         ctypes.POINTER(EbtPending))
 _PCOMM = ctypes.POINTER(EbtComm)
+_PALLOW = ctypes.POINTER(EbtAllow)
 _PSPEND = ctypes.POINTER(EbtShardedPending)
 
 _SIGNATURES = {
@@ -101,6 +107,20 @@ _SIGNATURES = {
     "ebt_cosine_topk_submit": ([_PCAT, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP, _POPT,
                                 _VP, _SZ, _VP, _VP, _VP, _PPEND, _VP, _VP], _INT),
     "ebt_cosine_topk_finish": ([_PPEND], _INT),
+    "ebt_allow_words": ([_I64], _I64),
+    "ebt_allow_from_bool": ([_VP, _I64, _VP, _I64, _VP], _INT),
+    "ebt_allow_set_rows": ([_VP, _I64, _VP, _I64, _INT, _VP], _INT),
+    "ebt_mask_allowed": ([_VP, _I64, _I64, _I64, _I64, _PALLOW, _VP], _INT),
+    "ebt_cosine_topk_prepared_allowed": ([_VP, _VP, _VP, _VP, _I64, _I64, _VP, _INT, _I64, _VP,
+                                          _VP, _VP, _INT, _I32, _I64, _I32, _I32, _I64, _VP, _VP,
+                                          _I32, _I32, _I64, _INT, _VP, _SZ, _VP, _VP, _VP, _VP,
+                                          _VP, _PALLOW], _INT),
+    "ebt_cosine_topk_allowed": ([_PCAT, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP, _POPT,
+                                 _VP, _SZ, _VP, _VP, _VP, _VP, _PALLOW], _INT),
+    "ebt_cosine_topk_allowed_submit": ([_PCAT, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP,
+                                        _POPT, _VP, _SZ, _VP, _VP, _VP, _PPEND, _VP, _VP,
+                                        _PALLOW], _INT),
+    "ebt_cosine_topk_allowed_finish": ([_PPEND, _PALLOW], _INT),
     "ebt_sharded_workspace_bytes": ([_PCAT, _PCOMM, _I64, _I32, _POPT], _SZ),
     "ebt_cosine_topk_sharded": ([_PCAT, _PCOMM, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP,
                                  _POPT, _VP, _SZ, _VP, _VP, _VP, _VP], _INT),

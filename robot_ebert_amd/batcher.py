@@ -27,6 +27,12 @@ concurrently, SURVEY §8b "Threading") only the dispatcher does.
   the edit is applied, then collection resumes (ebert.h: an update must not overtake a batch
   whose finish has not returned).
 
+* Filtered requests: with ``allow_masks=`` (allow.AllowMasks) a request may name one mask
+  (``submit(..., allow=index or name)``) and is answered from the rows that mask allows. A batch
+  with no filtered request takes the usual path; one with at least one runs as ONE batch through
+  ``score_topk_submit(..., allow=(masks, ids))`` with -1 for its unfiltered members. ``remove``
+  also remaps the masks (``AllowMasks.apply_moves``) inside the same barrier.
+
 Per-request semantics are those of ``lib.get_user_recs``: a request without liked rows fails
 with sklearn's ValueError (alone -- the rest of its batch is unaffected), results are
 (scores float64, global rows int64) ordered (score desc, row asc).
@@ -82,7 +88,7 @@ class RecBatcher:
                  score_fn: Optional[Callable] = None, history: int = 1024,
                  max_inflight: int = 2, stager="auto", submit_fn: Optional[Callable] = None,
                  finish_fn: Optional[Callable] = None,
-                 stage_min_bytes: Optional[int] = None) -> None:
+                 stage_min_bytes: Optional[int] = None, allow_masks=None) -> None:
         """catalog: the ``Catalog`` every request scores against. score_fn(catalog, k, liked=,
         exclude=) -> (scores [B, k], rows [B, k]); default: ``search.score_topk_submit`` /
         ``score_topk_finish`` (or submit_fn / finish_fn) with up to ``max_inflight`` batches on
@@ -93,10 +99,13 @@ class RecBatcher:
         A route-sized batch (tens of users, tens of KB) goes in line: its copies take
         microseconds, and the staging's dozen host-side stream / event / pinned-buffer calls per
         batch cost more than they hide (round 6, tools/route_bench.py with and without: batched
-        scoring 10.1-11.0K requests/s staged vs 15.0-15.7K in line, profiles/r6/route/)."""
+        scoring 10.1-11.0K requests/s staged vs 15.0-15.7K in line, profiles/r6/route/).
+        allow_masks: the allow.AllowMasks that ``submit(..., allow=)`` indexes; a filtered batch
+        calls score_fn / submit_fn with one more keyword, ``allow=(allow_masks, ids)``."""
         if max_batch < 1:
             raise ValueError("max_batch must be >= 1")
         self.catalog = catalog
+        self.allow_masks = allow_masks
         self._submit_fn, self._finish_fn = submit_fn, finish_fn
         if stager == "auto":
             dev = getattr(catalog, "device", None)
@@ -131,10 +140,23 @@ class RecBatcher:
         self._thread.start()
 
     # ---- request side (any thread) -----------------------------------------------------------
-    def submit(self, liked_rows: Sequence[int], exclude_rows: Sequence[int], k: int) -> Future:
+    def submit(self, liked_rows: Sequence[int], exclude_rows: Sequence[int], k: int,
+               allow=None) -> Future:
         """Queue one user's request; the Future resolves to (scores [k'], rows [k']) numpy arrays
-        (k' <= k: fewer when the catalog has fewer candidates) or raises the request's error."""
+        (k' <= k: fewer when the catalog has fewer candidates) or raises the request's error.
+        allow: None, or the index or name of one of ``allow_masks``: only the rows that mask
+        allows are candidates. A bad index or name fails this request alone."""
         fut: Future = Future()
+        mask = -1
+        if allow is not None:
+            if self.allow_masks is None:
+                fut.set_exception(ValueError("allow= needs a batcher built with allow_masks="))
+                return fut
+            try:
+                mask = int(self.allow_masks.index(allow))
+            except Exception as e:  # noqa: BLE001 -- EbertError: unknown name, index out of range
+                fut.set_exception(ValueError(f"bad allow mask: {e}"))
+                return fut
         # every request is checked HERE, before it can share a batch: the batch is one library
         # call, and an argument the library rejects (a liked row outside the catalog, a k whose
         # workspace cannot exist) would fail every co-batched request, other clients' included
@@ -166,7 +188,7 @@ class RecBatcher:
         if n > 0:
             rated = [r for r in rated if lo <= r < hi]
             k = min(k, int(getattr(self.catalog, "n_global", n)))
-        item = (liked, sorted(set(rated)), k, fut)
+        item = (liked, sorted(set(rated)), k, fut, mask)
         with self._lock:   # a request is either queued before close()'s sentinel or refused
             if self._closed:
                 fut.set_exception(RuntimeError("batcher is closed"))
@@ -283,6 +305,8 @@ class RecBatcher:
                     self._slots.acquire()
                     held += 1
             result = getattr(self.catalog, edit.method)(*edit.args)
+            if edit.method == "remove" and self.allow_masks is not None:
+                self.allow_masks.apply_moves(result, self.catalog.n)
         except BaseException as e:  # noqa: BLE001 -- the edit's error goes to its caller
             _answer(edit.fut, exc=e)
         else:
@@ -309,9 +333,13 @@ class RecBatcher:
     def _dispatch(self, reqs: list) -> None:
         k_max = max(r[2] for r in reqs)
         liked, excl = [r[0] for r in reqs], [r[1] for r in reqs]
+        # a batch with no filtered request takes the usual call, without the keyword
+        kw = {}
+        if any(r[4] >= 0 for r in reqs):
+            kw["allow"] = (self.allow_masks, [r[4] for r in reqs])
         if not self._pipelined:
             try:
-                scores, rows = self._score(self.catalog, k_max, liked=liked, exclude=excl)
+                scores, rows = self._score(self.catalog, k_max, liked=liked, exclude=excl, **kw)
             except BaseException as e:  # the whole batch failed: every caller sees the error
                 for r in reqs:
                     _answer(r[3], exc=e)
@@ -334,10 +362,10 @@ class RecBatcher:
                 dev = self.catalog.device
                 liked = csr_from_lists(liked, dev, self.stager)
                 excl = csr_from_lists(excl, dev, self.stager)
-                p = submit(self.catalog, k_max, liked=liked, exclude=excl)
+                p = submit(self.catalog, k_max, liked=liked, exclude=excl, **kw)
                 ev = self.stager.record()
             else:
-                p = submit(self.catalog, k_max, liked=liked, exclude=excl)
+                p = submit(self.catalog, k_max, liked=liked, exclude=excl, **kw)
         except BaseException as e:
             self._slots.release()
             for r in reqs:
@@ -394,7 +422,7 @@ class RecBatcher:
                 _answer(r[3], exc=e)
             return
         self._record(len(reqs))
-        for i, (_, _, k, fut) in enumerate(reqs):
+        for i, (_, _, k, fut, *_m) in enumerate(reqs):
             s, r = scores[i, :k], rows[i, :k]
             keep = r >= 0
             _answer(fut, (s[keep], r[keep]))

@@ -120,6 +120,8 @@ int query_prep(const void*, int, int64_t, int64_t, int32_t, int64_t, int, int, f
                void*, int32_t, float*, float*, hipStream_t);
 int mask_excluded(float*, int64_t, int64_t, int64_t, int64_t, const int64_t*, const int64_t*,
                   hipStream_t);
+int mask_allowed(float*, int64_t, int64_t, int64_t, int64_t, const ebt_allow*, hipStream_t);
+int check_allow(const ebt_allow*, int64_t row_end, const char* who);
 int rescore(const double*, int64_t, int32_t, const void*, int, int64_t, const double*, int64_t,
             const float*, const int64_t*, int32_t, int32_t, int64_t, const float*, const double*,
             double*, int64_t*, int32_t*, hipStream_t, const int*, int, unsigned long long*,
@@ -623,7 +625,8 @@ static int head_topk(const WsLayout& L, char* ws, const void* qimg, const float*
                      int img_dtype, int32_t ld_img, int64_t r0, int64_t nrows, int32_t d_pad,
                      int64_t row_offset, const int64_t* excl_off, const int64_t* excl_rows,
                      int32_t kprime, float* dv_final, int64_t* di_final, int64_t ld_final,
-                     void* timer, hipStream_t st, const ExactScreen* ex = nullptr) {
+                     void* timer, hipStream_t st, const ExactScreen* ex = nullptr,
+                     const ebt_allow* allow = nullptr) {
   float* S = (float*)(ws + L.off_s);
   float* segv = (float*)(ws + L.off_segv);
   int64_t* segi = (int64_t*)(ws + L.off_segi);
@@ -646,10 +649,14 @@ static int head_topk(const WsLayout& L, char* ws, const void* qimg, const float*
       }
     }
     if (rc) return rc;
-    if (excl_off) {
+    if (excl_off || allow) {
       StageScope s(timer, EBT_STAGE_MASK, st);
-      rc = mask_excluded(S, L.ld_s, B, row_offset + c0, row_offset + c0 + nc, excl_off,
-                         excl_rows, st);
+      rc = excl_off ? mask_excluded(S, L.ld_s, B, row_offset + c0, row_offset + c0 + nc,
+                                    excl_off, excl_rows, st)
+                    : EBT_OK;
+      // per-query allow masks (allow_mask.hip): the rows a filtered query may not see
+      if (!rc && allow)
+        rc = mask_allowed(S, L.ld_s, B, row_offset + c0, row_offset + c0 + nc, allow, st);
       if (rc) return rc;
     }
     float* dv = n_chunks == 1 ? dv_final : chv + c * kprime;
@@ -701,7 +708,7 @@ using namespace ebt;
 
 extern "C" {
 
-int ebt_version(void) { return 500; }  // 0.5.0: catalog rows removed in place (ebert.h)
+int ebt_version(void) { return 600; }  // 0.6.0: per-query allow masks (ebert.h)
 
 const char* ebt_last_error(void) { return g_err; }
 
@@ -929,6 +936,9 @@ struct PipeArgs {
   // layout) written by the screen's last wave merge
   float* floor_out = nullptr;
   int floor_w = 0;
+  // ebt_cosine_topk_prepared_allowed: the per-query allow masks (unfused and float64 screens
+  // only: the entry sets EBT_FLAG_NO_FUSE), null = unfiltered
+  const ebt_allow* allow = nullptr;
 };
 
 static int check_pipe(const PipeArgs& a, const char* who) {
@@ -1168,12 +1178,12 @@ static int run_screen(const PipeArgs& a, const WsLayout& L, char* ws, float* fv,
     so->eps = xeps;
     return head_topk(L, ws, nullptr, nullptr, B, B_pad, nullptr, nullptr, a.img_dtype, ld_img, 0,
                      n_rows, d_pad, row_offset, a.excl_off, a.excl_rows, kprime, fv, fi, kprime,
-                     timer, st, &ex);
+                     timer, st, &ex, a.allow);
   }
   if (!L.fused)
     return head_topk(L, ws, a.qimg, a.qscale, B, B_pad, a.cimg, a.cscale, a.img_dtype, ld_img, 0,
                      n_rows, d_pad, row_offset, a.excl_off, a.excl_rows, kprime, fv, fi, kprime,
-                     timer, st);
+                     timer, st, nullptr, a.allow);
   uint64_t* cand = (uint64_t*)(ws + L.off_cand);
   uint8_t* counts = (uint8_t*)(ws + L.off_counts);
   float* thr = (float*)(ws + L.off_thr);
@@ -1254,27 +1264,39 @@ static int run_screen(const PipeArgs& a, const WsLayout& L, char* ws, float* fv,
 
 extern "C" {
 
-int ebt_cosine_topk_prepared(const double* q64, const void* qimg, const float* qscale, const float* eps,
-                    int64_t B, int64_t B_pad, const void* cat, int dtype, int64_t ld,
-                    const double* gnorm64, const void* cimg, const float* cscale, int img_dtype,
-                    int32_t ld_img, int64_t n_rows, int32_t d, int32_t d_pad, int64_t row_offset,
-                    const int64_t* excl_off, const int64_t* excl_rows, int32_t k, int32_t kprime,
-                    int64_t chunk_rows, int flags, void* workspace, size_t ws_bytes,
-                    double* out_scores, int64_t* out_rows, int32_t* certified, void* timer,
-                    void* stream) {
+// ebt_cosine_topk_prepared, and with per-query allow masks ebt_cosine_topk_prepared_allowed:
+// allow != NULL runs the unfused screen (EBT_FLAG_NO_FUSE set here), its chunks masked twice
+static int cosine_topk_prepared_impl(
+    const char* who, const double* q64, const void* qimg, const float* qscale, const float* eps,
+    int64_t B, int64_t B_pad, const void* cat, int dtype, int64_t ld, const double* gnorm64,
+    const void* cimg, const float* cscale, int img_dtype, int32_t ld_img, int64_t n_rows,
+    int32_t d, int32_t d_pad, int64_t row_offset, const int64_t* excl_off,
+    const int64_t* excl_rows, int32_t k, int32_t kprime, int64_t chunk_rows, int flags,
+    void* workspace, size_t ws_bytes, double* out_scores, int64_t* out_rows, int32_t* certified,
+    void* timer, void* stream, const ebt_allow* allow) {
   hipStream_t st = (hipStream_t)stream;
-  const PipeArgs a{q64, qimg, qscale, eps, B, B_pad, cat, dtype, ld, gnorm64, cimg, cscale,
-                   img_dtype, ld_img, n_rows, d, d_pad, row_offset, excl_off, excl_rows, k, kprime,
-                   chunk_rows, flags};
-  int rc = check_pipe(a, "ebt_cosine_topk_prepared");
+  if (allow) flags |= EBT_FLAG_NO_FUSE;
+  PipeArgs a{q64, qimg, qscale, eps, B, B_pad, cat, dtype, ld, gnorm64, cimg, cscale,
+             img_dtype, ld_img, n_rows, d, d_pad, row_offset, excl_off, excl_rows, k, kprime,
+             chunk_rows, flags};
+  a.allow = allow;
+  int rc = check_pipe(a, who);
   if (rc) return rc;
   if (!workspace || !out_scores || !out_rows || !certified) {
-    set_error("ebt_cosine_topk_prepared: null pointer");
+    set_error("%s: null pointer", who);
     return EBT_EINVAL;
+  }
+  if (allow) {
+    if (row_offset < 0) {
+      set_error("%s: row_offset=%lld < 0", who, (long long)row_offset);
+      return EBT_EINVAL;
+    }
+    rc = check_allow(allow, row_offset + n_rows, who);
+    if (rc) return rc;
   }
   const WsLayout L = ws_layout(B, B_pad, n_rows, kprime, chunk_rows, flags);
   if (ws_bytes < L.bytes) {
-    set_error("ebt_cosine_topk_prepared: workspace %zu < %zu bytes", ws_bytes, L.bytes);
+    set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, L.bytes);
     return EBT_ENOMEM;
   }
   char* ws = (char*)workspace;
@@ -1289,6 +1311,38 @@ int ebt_cosine_topk_prepared(const double* q64, const void* qimg, const float* q
   return rescore(q64, B, d, cat, dtype, ld, gnorm64, row_offset, fv, fi, kprime, k, n_rows,
                  so.eps, nullptr, out_scores, out_rows, certified, st, so.ovf, 0,
                  timer_rows(timer, st), 0, nullptr, excl_off, excl_rows);
+}
+
+int ebt_cosine_topk_prepared(const double* q64, const void* qimg, const float* qscale, const float* eps,
+                    int64_t B, int64_t B_pad, const void* cat, int dtype, int64_t ld,
+                    const double* gnorm64, const void* cimg, const float* cscale, int img_dtype,
+                    int32_t ld_img, int64_t n_rows, int32_t d, int32_t d_pad, int64_t row_offset,
+                    const int64_t* excl_off, const int64_t* excl_rows, int32_t k, int32_t kprime,
+                    int64_t chunk_rows, int flags, void* workspace, size_t ws_bytes,
+                    double* out_scores, int64_t* out_rows, int32_t* certified, void* timer,
+                    void* stream) {
+  return cosine_topk_prepared_impl("ebt_cosine_topk_prepared", q64, qimg, qscale, eps, B, B_pad,
+                                   cat, dtype, ld, gnorm64, cimg, cscale, img_dtype, ld_img,
+                                   n_rows, d, d_pad, row_offset, excl_off, excl_rows, k, kprime,
+                                   chunk_rows, flags, workspace, ws_bytes, out_scores, out_rows,
+                                   certified, timer, stream, nullptr);
+}
+
+int ebt_cosine_topk_prepared_allowed(
+    const double* q64, const void* qimg, const float* qscale, const float* eps, int64_t B,
+    int64_t B_pad, const void* cat, int dtype, int64_t ld, const double* gnorm64,
+    const void* cimg, const float* cscale, int img_dtype, int32_t ld_img, int64_t n_rows,
+    int32_t d, int32_t d_pad, int64_t row_offset, const int64_t* excl_off,
+    const int64_t* excl_rows, int32_t k, int32_t kprime, int64_t chunk_rows, int flags,
+    void* workspace, size_t ws_bytes, double* out_scores, int64_t* out_rows, int32_t* certified,
+    void* timer, void* stream, const ebt_allow* allow) {
+  return cosine_topk_prepared_impl(allow ? "ebt_cosine_topk_prepared_allowed"
+                                         : "ebt_cosine_topk_prepared",
+                                   q64, qimg, qscale, eps, B, B_pad, cat, dtype, ld, gnorm64,
+                                   cimg, cscale, img_dtype, ld_img, n_rows, d, d_pad, row_offset,
+                                   excl_off, excl_rows, k, kprime, chunk_rows, flags, workspace,
+                                   ws_bytes, out_scores, out_rows, certified, timer, stream,
+                                   allow);
 }
 
 int ebt_cosine_screen(const double* q64, const void* qimg, const float* qscale, const float* eps,

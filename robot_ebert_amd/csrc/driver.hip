@@ -48,6 +48,8 @@ int pool_kth(const float*, int64_t, int64_t, int64_t, int, int, float*, hipStrea
              int64_t*, int, int*, const float*, int64_t, int, uint64_t*, int64_t, int, uint8_t*,
              int64_t, int, int64_t);
 
+int check_allow(const ebt_allow*, int64_t row_end, const char* who);
+
 namespace {
 
 constexpr int64_t KPRIME_MAX = 4096;
@@ -135,7 +137,8 @@ PrepLayout prep_layout(const ebt_catalog& c, int64_t rows) {
 
 // The whole workspace of one batch:
 //   [prep B] [pass: max(first pass, every retry pass)] [results k_eff < k] [cert B + flag]
-//   [retry: prep R, results R x k_eff, cert R, gather indices, exclusion CSR of the group]
+//   [retry: prep R, results R x k_eff, cert R, gather indices, exclusion CSR of the group,
+//    allow-mask ids of the group]
 // large: min(k, n) > 4096, the full-sort path (large_k.hip): [prep B] [sort buffers] [cert B + flag]
 struct DriverLayout {
   int64_t B, B_pad, R, chunk, chunk_r;
@@ -143,7 +146,7 @@ struct DriverLayout {
   bool large;
   PrepLayout prep, prep_r;
   size_t off_prep, off_pass, pass_bytes, off_res_s, off_res_r, off_cert, off_rprep, off_rs,
-      off_rr, off_rcert, off_idx, off_roff, off_rrows, off_big, big_bytes, bytes;
+      off_rr, off_rcert, off_idx, off_roff, off_rrows, off_rmask, off_big, big_bytes, bytes;
 };
 
 bool driver_layout(const ebt_catalog& c, int64_t B, int32_t k, const ebt_options& opt,
@@ -228,6 +231,8 @@ bool driver_layout(const ebt_catalog& c, int64_t B, int32_t k, const ebt_options
   o = al(o + (size_t)(D.R + 1) * 8);
   D.off_rrows = o;
   o = al(o + (size_t)RETRY_EXCL_MAX * 8);
+  D.off_rmask = o;  // (ebt_cosine_topk_allowed_finish: the retried queries' mask ids, int32)
+  o = al(o + (size_t)D.R * 4);
   D.bytes = o;
   return true;
 }
@@ -389,15 +394,16 @@ int prep_liked(const ebt_catalog& c, const int64_t* off, const int64_t* rows, in
 int run_prepared(const ebt_catalog& c, const PrepLayout& P, char* base, int64_t B,
                  const int64_t* excl_off, const int64_t* excl_rows, int32_t k_eff, int32_t kp,
                  int64_t chunk, int flags, char* pass, size_t pass_bytes, double* out_s,
-                 int64_t* out_r, int32_t* cert, void* timer, hipStream_t st) {
+                 int64_t* out_r, int32_t* cert, void* timer, hipStream_t st,
+                 const ebt_allow* allow) {
   const bool exact = flags & EBT_FLAG_EXACT;
-  return ebt_cosine_topk_prepared(
+  return ebt_cosine_topk_prepared_allowed(
       (const double*)(base + P.q64), exact ? nullptr : base + P.qimg,
       exact ? nullptr : (const float*)(base + P.qscale),
       exact ? nullptr : (const float*)(base + P.eps), B, pad_batch(B), c.data, c.dtype, c.ld,
       c.gnorm64, c.image, c.cscale, c.img_dtype, c.ld_img, c.n, c.d, c.d_pad, c.row_offset,
       excl_off, excl_rows, k_eff, kp, chunk, flags, pass, pass_bytes, out_s, out_r, cert, timer,
-      st);
+      st, allow);
 }
 
 bool valid_catalog(const ebt_catalog* c) {
@@ -779,12 +785,15 @@ size_t ebt_workspace_bytes(const ebt_catalog* cat, int64_t B, int32_t k, const e
   return L.bytes;
 }
 
-int ebt_cosine_topk_submit(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
-                           int64_t ldq, const int64_t* liked_off, const int64_t* liked_rows,
-                           int32_t k, const int64_t* excl_off, const int64_t* excl_rows,
-                           const ebt_options* opt, void* workspace, size_t ws_bytes,
-                           double* out_scores, int64_t* out_rows, int32_t* cert_host,
-                           ebt_pending* p, void* timer, void* stream) {
+// ebt_cosine_topk_submit (allow = NULL) and ebt_cosine_topk_allowed_submit: with per-query allow
+// masks the batch runs unfused (EBT_FLAG_NO_FUSE set here, and kept in the pending batch)
+static int cosine_topk_submit_impl(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                                   int64_t ldq, const int64_t* liked_off,
+                                   const int64_t* liked_rows, int32_t k, const int64_t* excl_off,
+                                   const int64_t* excl_rows, const ebt_options* opt,
+                                   void* workspace, size_t ws_bytes, double* out_scores,
+                                   int64_t* out_rows, int32_t* cert_host, ebt_pending* p,
+                                   void* timer, void* stream, const ebt_allow* allow) {
   hipStream_t st = (hipStream_t)stream;
   if (!valid_catalog(cat) || !p || !workspace || !out_scores || !out_rows || !cert_host ||
       B < 1 || k < 1 || ((q == nullptr) == (liked_off == nullptr)) ||
@@ -794,7 +803,16 @@ int ebt_cosine_topk_submit(const ebt_catalog* cat, const void* q, int q_dtype, i
               (long long)B, k);
     return EBT_EINVAL;
   }
-  const ebt_options o = opt ? *opt : ebt_options{};
+  ebt_options o = opt ? *opt : ebt_options{};
+  if (allow) {
+    if (cat->row_offset < 0) {
+      set_error("ebt_cosine_topk_allowed: catalog row_offset < 0");
+      return EBT_EINVAL;
+    }
+    const int rca = check_allow(allow, cat->row_offset + cat->n, "ebt_cosine_topk_allowed");
+    if (rca) return rca;
+    o.flags |= EBT_FLAG_NO_FUSE;
+  }
   DriverLayout L;
   if (!driver_layout(*cat, B, k, o, &L)) {
     set_error("ebt_cosine_topk: unsupported sizes or options (B=%lld k=%d n=%lld: n < 2^31; "
@@ -806,6 +824,11 @@ int ebt_cosine_topk_submit(const ebt_catalog* cat, const void* q, int q_dtype, i
     set_error("ebt_cosine_topk: workspace %zu < %zu bytes (ebt_workspace_bytes)", ws_bytes,
               L.bytes);
     return EBT_ENOMEM;
+  }
+  if (allow && L.large) {
+    set_error("ebt_cosine_topk_allowed: min(k, n) = %d > 4096 takes the full-sort path, which "
+              "has no allow masks", L.k_eff);
+    return EBT_EUNSUPPORTED;
   }
   char* ws = (char*)workspace;
   char* prep = ws + L.off_prep;
@@ -833,7 +856,7 @@ int ebt_cosine_topk_submit(const ebt_catalog* cat, const void* q, int q_dtype, i
     double* rs = padded ? (double*)(ws + L.off_res_s) : out_scores;
     int64_t* rr = padded ? (int64_t*)(ws + L.off_res_r) : out_rows;
     rc = run_prepared(*cat, L.prep, prep, B, excl_off, excl_rows, L.k_eff, L.kprime, L.chunk,
-                      L.flags, ws + L.off_pass, L.pass_bytes, rs, rr, cert, timer, st);
+                      L.flags, ws + L.off_pass, L.pass_bytes, rs, rr, cert, timer, st, allow);
   }
   if (rc) return rc;
   // the exclusion check: the rescore's certificate -3 (ebt_cosine_topk_prepared); the full-sort
@@ -883,10 +906,41 @@ int ebt_cosine_topk_submit(const ebt_catalog* cat, const void* q, int q_dtype, i
   return EBT_OK;
 }
 
-int ebt_cosine_topk_finish(ebt_pending* p) {
+int ebt_cosine_topk_submit(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                           int64_t ldq, const int64_t* liked_off, const int64_t* liked_rows,
+                           int32_t k, const int64_t* excl_off, const int64_t* excl_rows,
+                           const ebt_options* opt, void* workspace, size_t ws_bytes,
+                           double* out_scores, int64_t* out_rows, int32_t* cert_host,
+                           ebt_pending* p, void* timer, void* stream) {
+  return cosine_topk_submit_impl(cat, q, q_dtype, B, ldq, liked_off, liked_rows, k, excl_off,
+                                 excl_rows, opt, workspace, ws_bytes, out_scores, out_rows,
+                                 cert_host, p, timer, stream, nullptr);
+}
+
+int ebt_cosine_topk_allowed_submit(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                                   int64_t ldq, const int64_t* liked_off,
+                                   const int64_t* liked_rows, int32_t k, const int64_t* excl_off,
+                                   const int64_t* excl_rows, const ebt_options* opt,
+                                   void* workspace, size_t ws_bytes, double* out_scores,
+                                   int64_t* out_rows, int32_t* cert_host, ebt_pending* p,
+                                   void* timer, void* stream, const ebt_allow* allow) {
+  return cosine_topk_submit_impl(cat, q, q_dtype, B, ldq, liked_off, liked_rows, k, excl_off,
+                                 excl_rows, opt, workspace, ws_bytes, out_scores, out_rows,
+                                 cert_host, p, timer, stream, allow);
+}
+
+// ebt_cosine_topk_finish (allow = NULL) and ebt_cosine_topk_allowed_finish: a retried group's
+// mask ids are gathered through d_idx like its prepared rows, and the retry runs with an
+// ebt_allow pointing at them
+static int cosine_topk_finish_impl(ebt_pending* p, const ebt_allow* allow) {
   if (!p || !p->event || !p->cat) {
     set_error("ebt_cosine_topk_finish: not a submitted batch");
     return EBT_EINVAL;
+  }
+  if (allow) {
+    const int rca = check_allow(allow, p->cat->row_offset + p->cat->n,
+                                "ebt_cosine_topk_allowed_finish");
+    if (rca) return rca;
   }
   hipStream_t st = (hipStream_t)p->stream;
   const ebt_catalog& c = *p->cat;
@@ -934,6 +988,12 @@ int ebt_cosine_topk_finish(ebt_pending* p) {
   double* r_s = (double*)(ws + L.off_rs);
   int64_t* r_r = (int64_t*)(ws + L.off_rr);
   int32_t* r_c = (int32_t*)(ws + L.off_rcert);
+  int32_t* d_rmask = (int32_t*)(ws + L.off_rmask);
+  ebt_allow r_allow{};
+  if (allow) {
+    r_allow = *allow;
+    r_allow.mask_id = d_rmask;
+  }
   const int64_t qrow = (int64_t)c.d * 8, irow = (int64_t)c.ld_img * 2;
   for (int round = 0;; ++round) {
     // next configuration of every query that needs one
@@ -1010,6 +1070,7 @@ int ebt_cosine_topk_finish(ebt_pending* p) {
       if (!rc) rc = move_rows(prep + L.prep.qscale, 4, rprep + RP.qscale, 4, d_idx, m, 4, false,
                               st);
       if (!rc) rc = move_rows(prep + L.prep.eps, 4, rprep + RP.eps, 4, d_idx, m, 4, false, st);
+      if (!rc && allow) rc = move_rows(allow->mask_id, 4, d_rmask, 4, d_idx, m, 4, false, st);
       if (rc) return rc;
       const int64_t* eo = nullptr;
       const int64_t* er = nullptr;
@@ -1033,7 +1094,7 @@ int ebt_cosine_topk_finish(ebt_pending* p) {
         }
       }
       rc = run_prepared(c, RP, rprep, m, eo, er, L.k_eff, gkp, L.chunk_r, gfl, ws + L.off_pass,
-                        L.pass_bytes, r_s, r_r, r_c, p->timer, st);
+                        L.pass_bytes, r_s, r_r, r_c, p->timer, st, allow ? &r_allow : nullptr);
       if (!rc) rc = move_rows(r_s, (int64_t)L.k_eff * 8, rs, (int64_t)L.k_eff * 8, d_idx, m,
                               (int64_t)L.k_eff * 8, true, st);
       if (!rc) rc = move_rows(r_r, (int64_t)L.k_eff * 8, rr, (int64_t)L.k_eff * 8, d_idx, m,
@@ -1059,20 +1120,37 @@ int ebt_cosine_topk_finish(ebt_pending* p) {
   return EBT_OK;
 }
 
+int ebt_cosine_topk_finish(ebt_pending* p) { return cosine_topk_finish_impl(p, nullptr); }
+
+int ebt_cosine_topk_allowed_finish(ebt_pending* p, const ebt_allow* allow) {
+  return cosine_topk_finish_impl(p, allow);
+}
+
+int ebt_cosine_topk_allowed(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                            int64_t ldq, const int64_t* liked_off, const int64_t* liked_rows,
+                            int32_t k, const int64_t* excl_off, const int64_t* excl_rows,
+                            const ebt_options* opt, void* workspace, size_t ws_bytes,
+                            double* out_scores, int64_t* out_rows, void* timer, void* stream,
+                            const ebt_allow* allow) {
+  std::vector<int32_t> cert((size_t)(B > 0 ? B : 0) + 1);
+  ebt_pending p{};
+  int rc = cosine_topk_submit_impl(cat, q, q_dtype, B, ldq, liked_off, liked_rows, k, excl_off,
+                                   excl_rows, opt, workspace, ws_bytes, out_scores, out_rows,
+                                   cert.data(), &p, timer, stream, allow);
+  if (rc) return rc;
+  rc = cosine_topk_finish_impl(&p, allow);
+  if (!rc) rc = hip_check(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+  return rc;
+}
+
 int ebt_cosine_topk(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B, int64_t ldq,
                     const int64_t* liked_off, const int64_t* liked_rows, int32_t k,
                     const int64_t* excl_off, const int64_t* excl_rows, const ebt_options* opt,
                     void* workspace, size_t ws_bytes, double* out_scores, int64_t* out_rows,
                     void* timer, void* stream) {
-  std::vector<int32_t> cert((size_t)(B > 0 ? B : 0) + 1);
-  ebt_pending p{};
-  int rc = ebt_cosine_topk_submit(cat, q, q_dtype, B, ldq, liked_off, liked_rows, k, excl_off,
-                                  excl_rows, opt, workspace, ws_bytes, out_scores, out_rows,
-                                  cert.data(), &p, timer, stream);
-  if (rc) return rc;
-  rc = ebt_cosine_topk_finish(&p);
-  if (!rc) rc = hip_check(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
-  return rc;
+  return ebt_cosine_topk_allowed(cat, q, q_dtype, B, ldq, liked_off, liked_rows, k, excl_off,
+                                 excl_rows, opt, workspace, ws_bytes, out_scores, out_rows,
+                                 timer, stream, nullptr);
 }
 
 }  // extern "C"

@@ -31,14 +31,18 @@ SIMILARITY_TOP_K = 10     # constants.py:21
 engine = None                              # constants.py:26 (caller-supplied SQLAlchemy Engine)
 movies_collab_catalog: Optional[Catalog] = None  # constants.py:55-56, resident in HBM
 movies_content_catalog: Optional[Catalog] = None  # the movies-content collection (constants.py:29-53)
+allow_masks = None                         # allow.AllowMasks over movies_collab_catalog (optional)
 _get_movies_override: Optional[Callable[[List[str]], List[Movie]]] = None
 
 
 def configure(engine=None, catalog: Optional[Catalog] = None,
               get_movies: Optional[Callable[[List[str]], List[Movie]]] = None,
-              content_catalog: Optional[Catalog] = None) -> None:
-    """Install the process-global resources (the reference builds them at import time)."""
+              content_catalog: Optional[Catalog] = None, allow_masks=None) -> None:
+    """Install the process-global resources (the reference builds them at import time).
+    allow_masks: the allow.AllowMasks that ``get_user_recs(..., allow=)`` indexes."""
     g = globals()
+    if allow_masks is not None:
+        g["allow_masks"] = allow_masks
     if engine is not None:
         g["engine"] = engine
     if catalog is not None:
@@ -126,15 +130,31 @@ def _hydrate(s: np.ndarray, r: np.ndarray) -> List[Recommendation]:
     return sorted(recommendations, key=lambda x: x.score, reverse=True)  # lib.py:63
 
 
-def get_user_recs(user_id: str, k: int = 10) -> List[Recommendation]:
+def _allow_of(allow):
+    """(allow_masks, [mask index]) for one filtered request; EbertError on a bad name or index."""
+    from ._lib import EbertError
+    if allow_masks is None:
+        raise EbertError("allow= needs lib.configure(allow_masks=...)")
+    return allow_masks, [allow_masks.index(allow)]
+
+
+def get_user_recs(user_id: str, k: int = 10, allow=None) -> List[Recommendation]:
     """GPU drop-in for lib.py:32-63 (same inputs, same outputs, same errors).
 
     Any k, as the reference's pandas `[:k]` (min(k, rows) > 4096 runs the full-sort path of
-    csrc/large_k.hip). On a row-sharded catalog min(k, rows) <= 4096."""
+    csrc/large_k.hip). On a row-sharded catalog min(k, rows) <= 4096.
+
+    allow: None (the reference's function), or the index or name of one of the configured
+    ``allow_masks``: the recommendations come from the rows that mask allows (unrated ones, as
+    always), min(k, rows) <= 4096."""
     req = _user_request(user_id)
     if req is None:
         return []
     liked, rated = req
+    if allow is not None:
+        scores, rows = score_topk(movies_collab_catalog, k, liked=[liked], exclude=[rated],
+                                  allow=_allow_of(allow))
+        return _hydrate(scores[0].cpu().numpy(), rows[0].cpu().numpy())
     scores, rows = score_topk(movies_collab_catalog, k, liked=[liked], exclude=[rated])  # :51-55
     return _hydrate(scores[0].cpu().numpy(), rows[0].cpu().numpy())
 
@@ -142,14 +162,19 @@ def get_user_recs(user_id: str, k: int = 10) -> List[Recommendation]:
 get_user_recs_gpu = get_user_recs  # SURVEY §8b's name for the drop-in
 
 
-def get_user_recs_batched(batcher, user_id: str, k: int = 10) -> List[Recommendation]:
+def get_user_recs_batched(batcher, user_id: str, k: int = 10,
+                          allow=None) -> List[Recommendation]:
     """``get_user_recs`` whose scoring step is coalesced with concurrent callers by a
     ``batcher.RecBatcher`` over ``movies_collab_catalog``: same SQL, same errors,
-    same ordering; the GPU sees one batch for many request threads."""
+    same ordering; the GPU sees one batch for many request threads. allow: a mask index or name
+    of the batcher's ``allow_masks`` (None: unfiltered)."""
     req = _user_request(user_id)
     if req is None:
         return []
     liked, rated = req
+    if allow is not None:
+        s, r = batcher.submit(liked, rated, k, allow=allow).result()
+        return _hydrate(s, r)
     s, r = batcher.submit(liked, rated, k).result()
     return _hydrate(s, r)
 

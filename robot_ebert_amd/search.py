@@ -287,12 +287,19 @@ def spec_plan(B: int, n: int, kprime: int, fuse: bool = True) -> Optional[dict]:
 def run_pipeline(catalog: Catalog, qb: QueryBatch, k: int, kprime: int,
                  exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                  chunk_rows: Optional[int] = None, timer: Optional[_lib.Timer] = None,
-                 workspace: Optional[torch.Tensor] = None, flags: int = 0):
+                 workspace: Optional[torch.Tensor] = None, flags: int = 0, allow=None):
     """One ebt_cosine_topk_prepared call. Returns (scores f64 [B,k], rows i64 [B,k], certified i32 [B]);
-    certified is 1 (exact), 0 (widen k') or -1 (fused candidate list overflowed: run unfused)."""
+    certified is 1 (exact), 0 (widen k') or -1 (fused candidate list overflowed: run unfused).
+    allow=(AllowMasks, mask_ids): ebt_cosine_topk_prepared_allowed, the unfused screen with the
+    per-query allow masks (EBT_FLAG_NO_FUSE is set here, as the entry does)."""
+    import ctypes
+    from .allow import resolve_allow
     dev = catalog.device
     st = stream_of(dev)
     B, B_pad = qb.B, qb.B_pad
+    ra = resolve_allow(allow, B, dev)
+    if ra is not None and not flags & _lib.EBT_FLAG_EXACT:
+        flags |= _lib.EBT_FLAG_NO_FUSE
     chunk = chunk_rows or _chunk_rows(catalog, B_pad, DEFAULT_SCORE_BUDGET)
     need = _lib.load().ebt_cosine_topk_workspace(B, B_pad, catalog.n, kprime, chunk, flags)
     if need == 0:
@@ -303,12 +310,16 @@ def run_pipeline(catalog: Catalog, qb: QueryBatch, k: int, kprime: int,
     out_r = torch.empty((B, k), dtype=torch.int64, device=dev)
     cert = torch.empty(B, dtype=torch.int32, device=dev)
     eo, er = (exclude if exclude is not None else (None, None))
-    call("ebt_cosine_topk_prepared", ptr(qb.q64), ptr(qb.qimg), ptr(qb.qscale), ptr(qb.eps), B, B_pad,
-         ptr(catalog.data), catalog.dtype_code, catalog.ld, ptr(catalog.gnorm), ptr(catalog.image),
-         ptr(catalog.cscale), catalog.img_dtype, catalog.ld_img, catalog.n, catalog.d,
-         catalog.d_pad, catalog.row_offset, ptr(eo), ptr(er), k, kprime, chunk, flags, ptr(workspace),
-         int(workspace.numel()), ptr(out_s), ptr(out_r), ptr(cert),
-         timer.handle if timer is not None else None, st)
+    args = (ptr(qb.q64), ptr(qb.qimg), ptr(qb.qscale), ptr(qb.eps), B, B_pad,
+            ptr(catalog.data), catalog.dtype_code, catalog.ld, ptr(catalog.gnorm), ptr(catalog.image),
+            ptr(catalog.cscale), catalog.img_dtype, catalog.ld_img, catalog.n, catalog.d,
+            catalog.d_pad, catalog.row_offset, ptr(eo), ptr(er), k, kprime, chunk, flags,
+            ptr(workspace), int(workspace.numel()), ptr(out_s), ptr(out_r), ptr(cert),
+            timer.handle if timer is not None else None, st)
+    if ra is None:
+        call("ebt_cosine_topk_prepared", *args)
+    else:
+        call("ebt_cosine_topk_prepared_allowed", *args, ctypes.byref(ra[0]))
     return out_s, out_r, cert
 
 
@@ -409,7 +420,7 @@ def score_topk_submit(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
                kprime: Optional[int] = None, chunk_rows: Optional[int] = None,
                timer: Optional[_lib.Timer] = None, liked_counts: Optional[torch.Tensor] = None,
                liked_sum_hook=None, fuse: bool = True,
-               t_floor_hook=None, theta_hook=None) -> "PendingTopk":
+               t_floor_hook=None, theta_hook=None, allow=None) -> "PendingTopk":
     """Enqueue the first pass of score_topk (see there) on the catalog's device and return
     without waiting for it: score_topk_finish(pending) waits, retries the queries whose
     certificate needs it and returns (scores, rows). Submitting batch i+1 before finishing
@@ -439,7 +450,20 @@ def score_topk_submit(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
     shard). Called exactly once per call, before the screen; when it returns a threshold and
     the fused wave-merge screen applies (k' <= 512), the shard is screened at theta
     (ebt_cosine_screen_at) and a query whose theta exceeds t_floor - eps is rerun unfused.
+
+    allow=(AllowMasks, mask_ids): per-query allow masks (allow.py, include/ebert.h 0.6.0).
+    mask_ids is a host list (a mask index or name per query, None or -1 = unfiltered; checked
+    here) or a device int32 [B]; a filtered query gets the top k of (allowed rows minus excluded
+    rows). The batch runs the unfused path (ebt_cosine_topk_allowed_submit). Row-sharded
+    catalogs are out of scope: with any of the hooks it raises EbertError.
     """
+    if allow is not None:
+        if t_floor_hook is not None or theta_hook is not None or liked_sum_hook is not None \
+                or liked_counts is not None:
+            raise EbertError("allow= is not supported with t_floor_hook / theta_hook / "
+                             "liked_sum_hook (row-sharded catalogs take no allow masks)")
+        return _submit_c(catalog, k, queries, liked, exclude, kprime, chunk_rows, timer, fuse,
+                         allow)
     if t_floor_hook is None and theta_hook is None and liked_sum_hook is None and \
             liked_counts is None:
         # one catalog (or a shard queried on its own): the C ABI's self-contained path
@@ -465,13 +489,14 @@ class PendingTopkC:
     ws: torch.Tensor
     cert_host: torch.Tensor
     keep: tuple
+    allow: Optional["_lib.EbtAllow"] = None   # ebt_cosine_topk_allowed_submit: again at _finish
 
 
 _SKLEARN_EMPTY = "Found array with 0 sample(s)"
 
 
 def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_rows, timer,
-              fuse) -> PendingTopkC:
+              fuse, allow=None) -> PendingTopkC:
     """score_topk_submit over ebt_cosine_topk_submit: query prep, the screen, the certificate
     and every retry run inside libebert (include/ebert.h); Python only owns the buffers."""
     import ctypes
@@ -501,6 +526,10 @@ def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_r
     if B < 1:
         raise EbertError("empty query batch")
     flags = 0 if fuse else _lib.EBT_FLAG_NO_FUSE
+    from .allow import resolve_allow
+    ra = resolve_allow(allow, B, dev)
+    if ra is not None:   # a filtered batch is unfused: the workspace is sized with the flag
+        flags |= _lib.EBT_FLAG_NO_FUSE
     if liked is not None and isinstance(lo_csr, SortedCSR) and lo_csr.checked_for(
             catalog.row_offset, catalog.row_offset + catalog.n):
         # checked on the host while building it: the C entry reads nothing back (no stream sync)
@@ -517,18 +546,22 @@ def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_r
     cert_host = torch.empty(B + 1, dtype=torch.int32, pin_memory=True)
     pend = _lib.EbtPending()
     eo, er = exclude if exclude is not None else (None, None)
+    args = (ctypes.byref(catalog.cstruct), q_ptr, q_dt, B, ldq, ptr(lo), ptr(lr), k, ptr(eo),
+            ptr(er), ctypes.byref(opt), ptr(ws), need, ptr(out_s), ptr(out_r), ptr(cert_host),
+            ctypes.byref(pend), timer.handle if timer is not None else None, stream_of(dev))
     try:
-        call("ebt_cosine_topk_submit", ctypes.byref(catalog.cstruct), q_ptr, q_dt, B, ldq,
-             ptr(lo), ptr(lr), k, ptr(eo), ptr(er), ctypes.byref(opt), ptr(ws), need,
-             ptr(out_s), ptr(out_r), ptr(cert_host), ctypes.byref(pend),
-             timer.handle if timer is not None else None, stream_of(dev))
+        if ra is None:
+            call("ebt_cosine_topk_submit", *args)
+        else:
+            call("ebt_cosine_topk_allowed_submit", *args, ctypes.byref(ra[0]))
     except EbertError as e:
         msg = str(e)
         if _SKLEARN_EMPTY in msg:   # lib.py:51 on a user without liked movies (sklearn)
             raise ValueError(msg[msg.index(_SKLEARN_EMPTY):]) from None
         raise
     return PendingTopkC(pend, catalog, opt, out_s, out_r, ws, cert_host,
-                        (queries, lo, lr, eo, er))
+                        (queries, lo, lr, eo, er) + (ra[1] if ra is not None else ()),
+                        ra[0] if ra is not None else None)
 
 
 def score_topk_stages(catalog: Catalog, k: int, queries: Optional[torch.Tensor] = None,
@@ -590,7 +623,10 @@ def score_topk_finish(p) -> Tuple[torch.Tensor, torch.Tensor]:
     """Wait for a submitted batch, run its retries, return (scores f64 [B, k], rows i64 [B, k])."""
     if isinstance(p, PendingTopkC):
         import ctypes
-        call("ebt_cosine_topk_finish", ctypes.byref(p.pending))
+        if p.allow is not None:
+            call("ebt_cosine_topk_allowed_finish", ctypes.byref(p.pending), ctypes.byref(p.allow))
+        else:
+            call("ebt_cosine_topk_finish", ctypes.byref(p.pending))
         return p.out_s, p.out_r
     catalog, qb, k, k_eff, kp = p.catalog, p.qb, p.k, p.k_eff, p.kprime
     exclude, chunk_rows, timer, flags, n_cap = p.exclude, p.chunk_rows, p.timer, p.flags, p.n_cap
@@ -648,14 +684,15 @@ def score_topk(catalog: Catalog, k: int, queries: Optional[torch.Tensor] = None,
                kprime: Optional[int] = None, chunk_rows: Optional[int] = None,
                timer: Optional[_lib.Timer] = None, liked_counts: Optional[torch.Tensor] = None,
                liked_sum_hook=None, fuse: bool = True,
-               t_floor_hook=None, theta_hook=None) -> Tuple[torch.Tensor, torch.Tensor]:
+               t_floor_hook=None, theta_hook=None,
+               allow=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k by cosine (mean cosine over liked rows) with exclusions: score_topk_submit +
     score_topk_finish (arguments and results as documented there)."""
     return score_topk_finish(score_topk_submit(
         catalog, k, queries=queries, liked=liked, exclude=exclude, kprime=kprime,
         chunk_rows=chunk_rows, timer=timer, liked_counts=liked_counts,
         liked_sum_hook=liked_sum_hook, fuse=fuse, t_floor_hook=t_floor_hook,
-        theta_hook=theta_hook))
+        theta_hook=theta_hook, allow=allow))
 
 
 @dataclass
