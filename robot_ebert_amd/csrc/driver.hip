@@ -1313,7 +1313,9 @@ bool shard_layout(const ebt_catalog& c, const ebt_comm& cm, int64_t B, int32_t k
   o = al(o + L.pack_bytes);
   L.off_precv = o;
   o = al(o + (size_t)R * L.pack_bytes);
-  L.off_incomplete = o;   // int32 "incomplete" flag, then the rescore's pack counter (u32)
+  // the merge's int32 "incomplete" flag, then a reserved u32 (nothing reads or writes it after
+  // union_floor has zeroed both)
+  L.off_incomplete = o;
   o = al(o + 8);
   L.bytes = o;
   return true;
@@ -1570,8 +1572,8 @@ int ebt_cosine_topk_sharded_submit(const ebt_catalog* cat, const ebt_comm* comm,
   }
   if (!rc) rc = sh_gather(cm, fsend, frecv, (size_t)B * (S.fw + 1) * 4, timer, st);
   if (rc) return rc;
-  // (the floor's launch also zeroes the merge's "incomplete" flag and the pack counter that
-  // the rescore and the finish use: no memset launch)
+  // (the floor's launch also zeroes the merge's "incomplete" flag and the reserved word after
+  // it: no memset launch)
   uint32_t* zero2 = (uint32_t*)(ws + S.off_incomplete);
   if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_SMALL, st);
   rc = union_floor(frecv, R, B, (int32_t)S.fw + 1, k, tfloor, st, zero2);
