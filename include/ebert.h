@@ -80,7 +80,10 @@ extern "C" {
  *        ebt_allow_set_rows, ebt_mask_allowed, ebt_cosine_topk_prepared_allowed,
  *        ebt_cosine_topk_allowed / _allowed_submit / _allowed_finish (additive; no existing
  *        struct or signature changes; ebt_workspace_bytes grows by the retry group's mask ids,
- *        at most 1 KiB). */
+ *        at most 1 KiB).
+ * 0.7.0: materialised sub-catalogs: ebt_allow_count, ebt_allow_rows_bytes, ebt_allow_rows,
+ *        ebt_catalog_gather_rows, ebt_sub_exclusions_bytes, ebt_sub_exclusions,
+ *        ebt_sub_rows_to_global (additive; no existing entry, struct or kernel changes). */
 int ebt_version(void);
 
 /* Message for the last non-zero return on this thread ("" if none). */
@@ -644,6 +647,94 @@ int ebt_cosine_topk_allowed_submit(const ebt_catalog* cat, const void* q, int q_
                                    int64_t* out_rows, int32_t* cert_host, ebt_pending* pending,
                                    void* timer, void* stream, const ebt_allow* allow);
 int ebt_cosine_topk_allowed_finish(ebt_pending* pending, const ebt_allow* allow);
+
+/* ---- materialised sub-catalogs (0.7.0): a sparse mask scored over its own rows --------------
+ * The _allowed entries above score every catalog row and then mask: their cost does not fall
+ * with the mask's density. A row's state does not depend on where the row is -- its norm, inverse
+ * norm and image row are functions of its values (the fact ebt_catalog_remove_rows relies on) --
+ * so the m allowed rows of one mask can be copied ONCE into a dense catalog of their own, the
+ * SUB-CATALOG, whose row i is the i-th allowed row in ascending order. Every scoring entry runs
+ * over it unchanged (ebt_cosine_topk and its fused screen included, allow == NULL), on m rows
+ * instead of n. The map sub row -> GLOBAL row is strictly increasing, so the order (score desc,
+ * row asc) is kept, and the float64 scores are those of the same rows in the parent, bit for bit
+ * (the rescore reads the same values and norms; give the copy the parent's row alignment, see
+ * ld_out). A caller keeps: the row list [m], the rank prefix [words], the sub-catalog's buffers.
+ * The copy is a snapshot: after the mask or the parent changes (ebt_allow_set_rows,
+ * ebt_allow_from_bool, ebt_catalog_update_rows / _append_rows / _remove_rows) build it again.
+ * Recipe for one filtered batch: dense queries go to ebt_cosine_topk(sub, ...) as they are;
+ * liked queries are prepared against the PARENT (liked rows need not be allowed:
+ * ebt_query_liked_sum, ebt_scale_rows_f64, ebt_query_image with the parent's u_cat) and run
+ * through ebt_cosine_topk_prepared over the sub-catalog; exclusions go through
+ * ebt_sub_exclusions; result rows come back through ebt_sub_rows_to_global.
+ *
+ * In all of these a mask row is uint32 [words] as in struct ebt_allow: words a positive multiple
+ * of 4, at most 2^26; 16-byte alignment is not required here. Only rows [0, n_rows) count: bits
+ * at or above n_rows are ignored (ebt_allow_from_bool can leave them set past the catalog's n).
+ * Host checks run before any GPU call and return EBT_EINVAL: NULL pointers, words not a positive
+ * multiple of 4, n_rows < 0 or > 32 * words, a workspace that is too small. Everything is
+ * enqueued on `stream`; nothing waits for it.
+ *
+ * ebt_allow_count: *count_out (device int64) = the allowed rows of the mask row below n_rows.
+ *
+ * ebt_allow_rows: the stream compaction of one mask row. rows_out (device int64 [cap]) receives
+ * the allowed rows < n_rows, ascending; *count_out (device int64) how many there are -- entries
+ * past cap are counted, not written (cap = 0: count and rank only, rows_out may be NULL);
+ * rank_out (device uint32 [words]) receives for each word the number of allowed rows < n_rows in
+ * all earlier words (the exclusive prefix of the words' popcounts). Two launches: per-workgroup
+ * popcount totals into ws (ebt_allow_rows_bytes(words) bytes; 0 = invalid words), then each
+ * workgroup sums the totals before it and scans its own words. Output positions are computed,
+ * not claimed: the result is deterministic and no atomic is used. */
+int ebt_allow_count(const uint32_t* mask_row, int64_t words, int64_t n_rows, int64_t* count_out,
+                    void* stream);
+size_t ebt_allow_rows_bytes(int64_t words);
+int ebt_allow_rows(const uint32_t* mask_row, int64_t words, int64_t n_rows, int64_t* rows_out,
+                   int64_t cap, uint32_t* rank_out, int64_t* count_out, void* ws, size_t ws_bytes,
+                   void* stream);
+
+/* The gather: ONE kernel, a wave per output row. Output row i is the parent's row rows[i] (device
+ * list of m GLOBAL rows, any order, duplicates allowed): its d matrix elements into
+ * data_out[i][0 .. d) (row stride ld_out elements; columns d .. ld_out are not written), its
+ * image row into image_out[i][0 .. ld_img) (ld_img = the parent's), gnorm64 and inv32; and
+ * inv32_out[m .. round_up(m, 128)) = 1.0f. Nothing is recomputed: the copies are bit-identical
+ * to what ebt_catalog_init computes for a matrix made of those rows with the parent's alignment.
+ * A rows[i] outside [row_offset, row_offset + n) is never followed: that output row is zero-filled
+ * with gnorm 1 and inv32 1, and nothing is read out of bounds.
+ *   data_out [m][ld_out] of the parent's dtype, gnorm_out [m], inv32_out [round_up(m, 128)],
+ *   image_out [m][ld_img] 16-bit, 16-byte aligned: device buffers of the caller, which must
+ *   outlive *sub. When the parent's matrix is its own image (parent->image == parent->data)
+ *   image_out is ignored (NULL), the sub-catalog's image is data_out, and ld_out must be a
+ *   multiple of 64 with data_out 16-byte aligned.
+ *   ld_out: the rescore picks its 16-byte form when the matrix is 16-byte aligned with
+ *   ld * elem % 16 == 0 and d * elem % 16 == 0; give the copy the same property as the parent
+ *   (ld_out = d, or the parent's ld, does when the parent is so aligned) and scores stay bitwise
+ *   equal; any ld_out >= d is correct.
+ * *sub (host) is filled before the call returns: n = m, row_offset = 0, data / ld / gnorm64 /
+ * inv32 / image the buffers above, dtype, d, img_dtype, d_pad and native the parent's, ld_img the
+ * parent's (ld_out when the matrix is its own image), cscale = inv32_out for a native parent and
+ * NULL otherwise, u_cat the parent's (a bound over all its rows, so over the copied ones).
+ * EBT_EINVAL before any GPU call: NULL pointers, m < 1, ld_out < d, a parent whose matrix is its
+ * own image with ld_out % 64 != 0, image_out NULL for a parent with an image of its own. */
+int ebt_catalog_gather_rows(const ebt_catalog* parent, const int64_t* rows, int64_t m,
+                            void* data_out, int64_t ld_out, double* gnorm_out, float* inv32_out,
+                            void* image_out, ebt_catalog* sub, void* stream);
+
+/* An exclusion CSR of GLOBAL rows (off [B + 1] positions into rows [nnz], each segment ascending,
+ * off[0] may be > 0) in the sub-catalog's row numbers: an allowed row r < n_rows becomes
+ * rank[r >> 5] + popcount(word[r >> 5] & ((1u << (r & 31)) - 1)), every other row is dropped.
+ * The output is a compact CSR, off_out [B + 1] with off_out[0] = 0 and rows_out (room for nnz
+ * entries), each segment still ascending (the map is increasing). Three launches: count per
+ * query, scan, write; ws of ebt_sub_exclusions_bytes(B, nnz) bytes (0 for B < 1, nnz < 0 or
+ * either above 2^31). Offsets pointing outside [0, nnz) are clipped, never followed. */
+size_t ebt_sub_exclusions_bytes(int64_t B, int64_t nnz);
+int ebt_sub_exclusions(const uint32_t* mask_row, int64_t words, const uint32_t* rank,
+                       int64_t n_rows, const int64_t* off, const int64_t* rows, int64_t B,
+                       int64_t nnz, int64_t* off_out, int64_t* rows_out, void* ws,
+                       size_t ws_bytes, void* stream);
+
+/* Result rows of a sub-catalog back to GLOBAL rows, in place (device int64 [count]): r < 0 stays
+ * -1, 0 <= r < m becomes list[r] (ebt_allow_rows' rows_out), anything else becomes -1. */
+int ebt_sub_rows_to_global(int64_t* rows_inout, int64_t count, const int64_t* list, int64_t m,
+                           void* stream);
 
 /* ---- row-sharded catalog, self-contained: one call per batch on every rank ---------------
  * The per-shard protocol of robot_ebert_amd/distributed.py (score_topk_sharded_local_stages)

@@ -11,11 +11,14 @@ holes from the tail and returning the moves ``(old_row, new_row)``; ``RecBatcher
 of a row-sharded catalog its part of an update.
 
 ``AllowMasks`` (ABI 0.6.0) restricts a query to a subset of the rows: ``score_topk(..., allow=(masks,
-mask_ids))`` returns the top k of (allowed rows minus excluded rows).
+mask_ids))`` returns the top k of (allowed rows minus excluded rows). A sparse mask can be
+materialised (ABI 0.7.0): ``masks.materialize(mask)`` copies its allowed rows into a dense
+sub-catalog (``SubCatalog``) and the queries of that mask are then scored over those rows alone,
+with the same rows and bitwise the same scores.
 """
 from ._lib import EbertError, Timer, load  # noqa: F401
 from .catalog import Catalog  # noqa: F401
-from .allow import AllowMasks  # noqa: F401
+from .allow import AllowMasks, SubCatalog  # noqa: F401
 from .search import (merge_topk, prepare_queries, rescore_rows, score_topk,  # noqa: F401
                      score_topk_finish, score_topk_submit)
 from . import ops  # noqa: F401,E402  (registers torch.ops.ebert.*)

@@ -121,6 +121,14 @@ _SIGNATURES = {
                                         _POPT, _VP, _SZ, _VP, _VP, _VP, _PPEND, _VP, _VP,
                                         _PALLOW], _INT),
     "ebt_cosine_topk_allowed_finish": ([_PPEND, _PALLOW], _INT),
+    "ebt_allow_count": ([_VP, _I64, _I64, _VP, _VP], _INT),
+    "ebt_allow_rows_bytes": ([_I64], _SZ),
+    "ebt_allow_rows": ([_VP, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _SZ, _VP], _INT),
+    "ebt_catalog_gather_rows": ([_PCAT, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _PCAT, _VP], _INT),
+    "ebt_sub_exclusions_bytes": ([_I64, _I64], _SZ),
+    "ebt_sub_exclusions": ([_VP, _I64, _VP, _I64, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _SZ, _VP],
+                           _INT),
+    "ebt_sub_rows_to_global": ([_VP, _I64, _VP, _I64, _VP], _INT),
     "ebt_sharded_workspace_bytes": ([_PCAT, _PCOMM, _I64, _I32, _POPT], _SZ),
     "ebt_cosine_topk_sharded": ([_PCAT, _PCOMM, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP,
                                  _POPT, _VP, _SZ, _VP, _VP, _VP, _VP], _INT),

@@ -6,10 +6,19 @@ intersects it with the rows its mask allows ("within this genre", "only this ten
 same bits; bit r of mask m = GLOBAL row r is allowed in m) and is passed to
 ``score_topk(..., allow=(masks, mask_ids))``; its bits are written by the library's kernels
 (ebt_allow_from_bool, ebt_allow_set_rows).
+
+A sparse mask can be MATERIALISED (include/ebert.h, 0.7.0): ``materialize(mask)`` copies its
+allowed rows once into a dense sub-catalog, and ``score_topk`` then scores the queries filtered by
+that mask over those m rows -- through every existing path, the fused screen included -- instead of
+over all n rows followed by the mask pass. Rows and float64 scores are the same, bit for bit; the
+copy costs m / n of the catalog's matrix and image, and is rebuilt after the mask or the catalog
+changes (a stale copy is never used: the mask pass answers).
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+import ctypes
+from dataclasses import dataclass
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -21,6 +30,23 @@ from ._lib import EbertError, call, ptr, require_cuda, stream_of
 def allow_words(n_rows: int) -> int:
     """ebt_allow_words: uint32 words of one mask row covering n_rows rows (a multiple of 4)."""
     return int(_lib.load().ebt_allow_words(int(n_rows)))
+
+
+def _round_up(v: int, m: int) -> int:
+    return (v + m - 1) // m * m
+
+
+@dataclass
+class SubCatalog:
+    """One materialised mask: its allowed rows as a catalog of their own (Catalog.from_parts over
+    the tensors ebt_catalog_gather_rows filled), the row list that maps its rows back to GLOBAL
+    rows and the rank prefix that maps GLOBAL rows into it."""
+    catalog: object            # the m-row Catalog
+    rows: torch.Tensor         # int64 [m]: GLOBAL row of sub-catalog row i, ascending
+    rank: torch.Tensor         # uint32 [words] (held as int32): allowed rows in all earlier words
+    m: int
+    n_rows: int                # the parent's n when it was built: bits at or above it are ignored
+    edits: int                 # the parent's edit counter when it was built
 
 
 class AllowMasks:
@@ -57,6 +83,7 @@ class AllowMasks:
         self.words = allow_words(n_rows)
         self.device = dev
         self.table = torch.zeros((self.n_masks, self.words), dtype=torch.int32, device=dev)
+        self._subs: Dict[int, SubCatalog] = {}   # materialised masks (materialize)
 
     # ---- lookups ------------------------------------------------------------------------------
     def index(self, name_or_index) -> int:
@@ -81,6 +108,7 @@ class AllowMasks:
         """Allow (or disallow) a list of GLOBAL rows -- or string ids of the catalog -- in one
         mask (ebt_allow_set_rows). Rows outside the table are refused here."""
         row = self._row(mask)
+        self._subs.pop(self.index(mask), None)   # its copy no longer matches the bits
         if isinstance(rows_or_ids, torch.Tensor):
             require_cuda(rows_or_ids, "rows")
             rows = rows_or_ids.to(torch.int64).contiguous().flatten()
@@ -109,6 +137,7 @@ class AllowMasks:
         """Replace one mask by a boolean (or uint8) vector over rows [0, len(flags)): non-zero =
         allowed, rows past it not allowed (ebt_allow_from_bool)."""
         row = self._row(mask)
+        self._subs.pop(self.index(mask), None)
         if not isinstance(flags, torch.Tensor):
             flags = torch.from_numpy(np.asarray(flags).astype(np.uint8)).to(self.device)
         require_cuda(flags, "flags")
@@ -130,6 +159,7 @@ class AllowMasks:
         if n_new < 0 or n_new > 32 * self.words:
             raise EbertError(f"n_new={n_new} is outside the table's rows")
         moves = [(int(s), int(t)) for s, t in moves]
+        self._subs.clear()   # every mask is touched
         for s, t in moves:
             if not (0 <= t < n_new <= s < 32 * self.words):
                 raise EbertError(f"move ({s}, {t}) is not one of a removal down to {n_new} rows")
@@ -155,11 +185,10 @@ class AllowMasks:
 
     # ---- readers ------------------------------------------------------------------------------
     def count(self, mask) -> int:
-        """Allowed rows of one mask."""
-        w = self._row(mask).to(torch.int64) & 0xffffffff
-        c = torch.zeros((), dtype=torch.int64, device=self.device)
-        for s in range(32):
-            c = c + ((w >> s) & 1).sum()
+        """Allowed rows of one mask (ebt_allow_count over all the table's rows)."""
+        c = torch.empty(1, dtype=torch.int64, device=self.device)
+        call("ebt_allow_count", ptr(self._row(mask)), self.words, 32 * self.words, ptr(c),
+             stream_of(self.device))
         return int(c.item())
 
     def to_bool(self, mask, n: Optional[int] = None) -> torch.Tensor:
@@ -168,15 +197,93 @@ class AllowMasks:
         r = torch.arange(n, dtype=torch.int64, device=self.device)
         return ((self._row(mask)[r >> 5] >> (r & 31).to(torch.int32)) & 1) != 0
 
+    # ---- materialised sub-catalogs (ebert.h 0.7.0) --------------------------------------------
+    def materialize(self, mask) -> int:
+        """Copy the allowed rows of one mask into a dense sub-catalog (ebt_allow_rows,
+        ebt_catalog_gather_rows) and return their number m. From then on ``score_topk(...,
+        allow=(masks, ids))`` with a HOST list of ids scores the queries of this mask over those
+        m rows -- same rows, bitwise the same scores. The copy holds m / n of the catalog's
+        matrix and image. It is a snapshot: ``set`` / ``from_bool`` / ``apply_moves`` on the mask
+        drop it and an edit of the catalog makes it stale (never used again; the mask pass
+        answers) until ``materialize`` is called again. m = 0 builds nothing (the mask stays on
+        the mask pass). Waits for the stream once (m sizes the buffers)."""
+        from .catalog import Catalog
+        mi = self.index(mask)
+        cat = self.catalog
+        if cat is None:
+            raise EbertError("materialize needs masks built for a Catalog, not for a row count")
+        if cat.row_offset != 0 or cat.n_global != cat.n:
+            raise EbertError("materialize on a row-sharded catalog is not supported")
+        self._subs.pop(mi, None)
+        dev, st = self.device, stream_of(self.device)
+        row = self.table[mi]
+        n_rows = min(int(cat.n), 32 * self.words)
+        cnt = torch.empty(1, dtype=torch.int64, device=dev)
+        call("ebt_allow_count", ptr(row), self.words, n_rows, ptr(cnt), st)
+        m = int(cnt.item())
+        if m == 0:
+            return 0
+        rows = torch.empty(m, dtype=torch.int64, device=dev)
+        rank = torch.empty(self.words, dtype=torch.int32, device=dev)
+        need = int(_lib.load().ebt_allow_rows_bytes(self.words))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        call("ebt_allow_rows", ptr(row), self.words, n_rows, ptr(rows), m, ptr(rank), ptr(cnt),
+             ptr(ws), need, st)
+        # the copy's row stride: the parent's when its matrix is its own image (one ld_img for
+        # the queries prepared on the parent), else d -- moved off 16-byte alignment when the
+        # parent's rows are not aligned, so that the rescore takes the same form on both
+        # (rescore.hip) and the scores stay bitwise equal
+        es = cat.data.element_size()
+        alias = int(cat.cstruct.image or 0) == int(cat.cstruct.data or 0)
+        if alias:
+            ld_out = cat.ld
+        else:
+            ld_out = cat.d
+            parent_vec = cat.data.data_ptr() % 16 == 0 and (cat.ld * es) % 16 == 0
+            if (cat.d * es) % 16 == 0 and not parent_vec:
+                ld_out = cat.d + 1
+        data = torch.empty((m, ld_out), dtype=cat.data.dtype, device=dev)
+        if ld_out > cat.d:
+            data.zero_()
+        gnorm = torch.empty(m, dtype=torch.float64, device=dev)
+        inv32 = torch.empty(_round_up(m, 128), dtype=torch.float32, device=dev)
+        image = None if alias else torch.empty((m, cat.ld_img), dtype=cat.img_torch_dtype,
+                                               device=dev)
+        sub = _lib.EbtCatalog()
+        call("ebt_catalog_gather_rows", ctypes.byref(cat.cstruct), ptr(rows), m, ptr(data), ld_out,
+             ptr(gnorm), ptr(inv32), ptr(image), ctypes.byref(sub), st)
+        view = Catalog.from_parts(data[:, :cat.d], gnorm, inv32, data if alias else image,
+                                  u_cat=float(sub.u_cat))
+        for f, _t in _lib.EbtCatalog._fields_:   # the library's struct and from_parts' agree
+            if getattr(view.cstruct, f) != getattr(sub, f):
+                raise EbertError(f"internal error: sub-catalog field {f} differs "
+                                 f"({getattr(view.cstruct, f)} vs {getattr(sub, f)})")
+        self._subs[mi] = SubCatalog(view, rows, rank, m, n_rows, int(cat.edits))
+        return m
+
+    def dematerialize(self, mask) -> None:
+        """Free the sub-catalog of one mask (no-op when it has none)."""
+        self._subs.pop(self.index(mask), None)
+
+    def materialized(self) -> Dict[int, Tuple[int, bool]]:
+        """mask index -> (rows of its sub-catalog, fresh): fresh = it matches the catalog's edit
+        counter and is used; a stale one is kept until ``materialize`` / ``dematerialize``."""
+        return {mi: (v.m, self._fresh(v)) for mi, v in sorted(self._subs.items())}
+
+    def _fresh(self, v: SubCatalog) -> bool:
+        return self.catalog is not None and v.edits == int(self.catalog.edits)
+
+    def sub_for(self, catalog, mask: int) -> Optional[SubCatalog]:
+        """The fresh sub-catalog of mask index `mask` for queries against `catalog`, or None."""
+        v = self._subs.get(mask)
+        if v is None or catalog is not self.catalog or not self._fresh(v):
+            return None
+        return v
+
     # ---- the C struct -------------------------------------------------------------------------
-    def mask_ids(self, ids, B: int) -> torch.Tensor:
-        """Device int32 [B] of per-query mask ids from a host list (None / -1 / a name / an index,
-        range-checked here) or a device int32 tensor (used as it is)."""
-        if isinstance(ids, torch.Tensor):
-            require_cuda(ids, "mask_ids")
-            if ids.dtype != torch.int32 or ids.dim() != 1 or ids.numel() != B:
-                raise EbertError(f"mask_ids must be int32 [{B}]")
-            return ids.contiguous()
+    def host_ids(self, ids, B: int) -> np.ndarray:
+        """int32 [B] of per-query mask ids from a host list (None / -1 / a name / an index,
+        range-checked here); -1 = unfiltered."""
         ids = list(ids)
         if len(ids) != B:
             raise EbertError(f"{len(ids)} mask ids for {B} queries")
@@ -186,7 +293,17 @@ class AllowMasks:
                 host[b] = -1
             else:
                 host[b] = self.index(m)
-        return torch.from_numpy(host).to(self.device)
+        return host
+
+    def mask_ids(self, ids, B: int) -> torch.Tensor:
+        """Device int32 [B] of per-query mask ids from a host list (None / -1 / a name / an index,
+        range-checked here) or a device int32 tensor (used as it is)."""
+        if isinstance(ids, torch.Tensor):
+            require_cuda(ids, "mask_ids")
+            if ids.dtype != torch.int32 or ids.dim() != 1 or ids.numel() != B:
+                raise EbertError(f"mask_ids must be int32 [{B}]")
+            return ids.contiguous()
+        return torch.from_numpy(self.host_ids(ids, B)).to(self.device)
 
     def cstruct(self, mask_id: torch.Tensor) -> "_lib.EbtAllow":
         return _lib.EbtAllow(masks=ptr(self.table), words=self.words, n_masks=self.n_masks,

@@ -31,7 +31,9 @@ concurrently, SURVEY §8b "Threading") only the dispatcher does.
   (``submit(..., allow=index or name)``) and is answered from the rows that mask allows. A batch
   with no filtered request takes the usual path; one with at least one runs as ONE batch through
   ``score_topk_submit(..., allow=(masks, ids))`` with -1 for its unfiltered members. ``remove``
-  also remaps the masks (``AllowMasks.apply_moves``) inside the same barrier.
+  also remaps the masks (``AllowMasks.apply_moves``) inside the same barrier. The ids are a host
+  list, so the requests of a materialised mask (``AllowMasks.materialize``) are scored over its
+  sub-catalog; every edit leaves those copies stale until the caller materialises again.
 
 Per-request semantics are those of ``lib.get_user_recs``: a request without liked rows fails
 with sklearn's ValueError (alone -- the rest of its batch is unaffected), results are

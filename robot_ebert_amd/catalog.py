@@ -108,6 +108,9 @@ class Catalog:
         if self.ids is not None and len(self.ids) != self.n:
             raise EbertError(f"{len(self.ids)} ids for {self.n} rows")
         self._pos: Optional[Dict[str, int]] = None
+        # bumped by every edit (update_rows / append / remove): what was derived from the rows
+        # (allow.AllowMasks' materialised sub-catalogs) is used only while it matches
+        self.edits = 0
 
     def _views(self) -> None:
         """The tensors the scoring code reads, over the first n rows of a state laid out for
@@ -189,6 +192,7 @@ class Catalog:
              DTYPE_CODE[vectors.dtype], int(vectors.stride(0)), ptr(ws), ws.numel(),
              stream_of(self.device))
         self.u_cat = float(self.cstruct.u_cat)
+        self.edits += 1
 
     def append(self, vectors, ids: Optional[Sequence[str]] = None) -> None:
         """Append rows in place, up to ``capacity``: n, n_global, the C struct, the ids and the
@@ -219,6 +223,7 @@ class Catalog:
         call("ebt_catalog_append_rows", ctypes.byref(self.cstruct), ptr(self.state),
              self.state.numel(), self.capacity, m, ptr(vectors), DTYPE_CODE[vectors.dtype],
              int(vectors.stride(0)), stream_of(self.device))
+        self.edits += 1
         self._views()
         self.n_global = self.n
         if ids is not None:
@@ -276,6 +281,7 @@ class Catalog:
         call("ebt_catalog_remove_rows", ctypes.byref(self.cstruct), ptr(self.state),
              self.state.numel(), self.capacity, host_rows.ctypes.data, m, ptr(ws), ws.numel(),
              stream_of(self.device))
+        self.edits += 1
         self._views()
         self.n_global = self.n
         if self.ids is not None:
@@ -312,10 +318,12 @@ class Catalog:
     @classmethod
     def from_parts(cls, emb: torch.Tensor, gnorm: torch.Tensor, inv32: torch.Tensor,
                    image: torch.Tensor, row_offset: int = 0,
-                   n_global: Optional[int] = None) -> "Catalog":
+                   n_global: Optional[int] = None, u_cat: Optional[float] = None) -> "Catalog":
         """A catalog view over tensors already built by ``row_norms`` / ``screen_image`` (the
         torch ops of ``ops.py``): nothing is recomputed. ``image`` is the f16 normalised image,
-        or the matrix itself for a native f16/bf16 catalog with d % 64 == 0."""
+        or the matrix itself for a native f16/bf16 catalog with d % 64 == 0. ``u_cat``: a bound
+        on the image rows' error known to the caller (a sub-catalog carries its parent's measured
+        value); default 0 for a 16-bit catalog, else the unit round-off 2^-11."""
         for t, what in ((emb, "catalog"), (gnorm, "gnorm"), (inv32, "inv"), (image, "image")):
             require_cuda(t, what)
         self = cls.__new__(cls)
@@ -340,11 +348,12 @@ class Catalog:
         self.image, self.ld_img = image, int(image.stride(0))
         self.img_dtype = EBT_F16 if image.dtype == torch.float16 else EBT_BF16
         self.native = native_16  # the image holds the raw rows, scaled by inv in the epilogue
-        self.u_cat = 0.0 if native_16 else 2.0 ** -11
+        self.u_cat = float(u_cat) if u_cat is not None else (0.0 if native_16 else 2.0 ** -11)
         self.cscale = self.inv32 if native_16 else None
         self.ids, self._pos = None, None
         self.state = None   # no state of the library's layout: update_rows / append refuse
         self._store, self.capacity = self.data, self.n
+        self.edits = 0
         self.cstruct = _lib.EbtCatalog(
             data=ptr(self.data), dtype=self.dtype_code, d=self.d, n=self.n, ld=self.ld,
             row_offset=self.row_offset, gnorm64=ptr(gnorm), inv32=ptr(inv32), image=ptr(image),

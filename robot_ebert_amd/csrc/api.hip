@@ -708,7 +708,7 @@ using namespace ebt;
 
 extern "C" {
 
-int ebt_version(void) { return 600; }  // 0.6.0: per-query allow masks (ebert.h)
+int ebt_version(void) { return 700; }  // 0.7.0: materialised sub-catalogs (ebert.h)
 
 const char* ebt_last_error(void) { return g_err; }
 

@@ -456,12 +456,22 @@ def score_topk_submit(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
     here) or a device int32 [B]; a filtered query gets the top k of (allowed rows minus excluded
     rows). The batch runs the unfused path (ebt_cosine_topk_allowed_submit). Row-sharded
     catalogs are out of scope: with any of the hooks it raises EbertError.
+    With a HOST list of ids, the queries of a mask that has a fresh sub-catalog
+    (AllowMasks.materialize, ebert.h 0.7.0) are grouped and scored over that sub-catalog -- m
+    rows instead of n, any path, the fused screen included; same rows, bitwise the same scores --
+    and the others (unfiltered, or masks without one) run as one sub-batch as described above.
+    The returned pending's ``routes`` lists (mask, query indices, sub-catalog rows) of every such
+    group (empty when none). A device tensor of ids always takes the mask pass.
     """
     if allow is not None:
         if t_floor_hook is not None or theta_hook is not None or liked_sum_hook is not None \
                 or liked_counts is not None:
             raise EbertError("allow= is not supported with t_floor_hook / theta_hook / "
                              "liked_sum_hook (row-sharded catalogs take no allow masks)")
+        routed = _submit_routed(catalog, k, queries, liked, exclude, kprime, chunk_rows, timer,
+                                fuse, allow)
+        if routed is not None:
+            return routed
         return _submit_c(catalog, k, queries, liked, exclude, kprime, chunk_rows, timer, fuse,
                          allow)
     if t_floor_hook is None and theta_hook is None and liked_sum_hook is None and \
@@ -490,6 +500,7 @@ class PendingTopkC:
     cert_host: torch.Tensor
     keep: tuple
     allow: Optional["_lib.EbtAllow"] = None   # ebt_cosine_topk_allowed_submit: again at _finish
+    routes: tuple = ()   # no sub-catalog answered (PendingRouted.routes otherwise)
 
 
 _SKLEARN_EMPTY = "Found array with 0 sample(s)"
@@ -564,6 +575,151 @@ def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_r
                         ra[0] if ra is not None else None)
 
 
+@dataclass
+class PendingRouted:
+    """A filtered batch whose queries were grouped by mask (_submit_routed): every group of a
+    materialised mask runs over that mask's sub-catalog, the rest as one sub-batch on the usual
+    path; score_topk_finish finishes the parts and scatters them into [B, k]."""
+    catalog: Catalog
+    B: int
+    k: int
+    parts: list     # (query indices int64 [b] on the device, the part's pending, SubCatalog | None)
+    routes: tuple   # (mask, [query indices], sub-catalog rows) of every group a sub-catalog answers
+
+
+def _take(x, idx_host, idx_dev):
+    """The queries idx of per-query host lists or of a device CSR (same kind back)."""
+    if x is None:
+        return None
+    if isinstance(x, tuple):
+        off, rows = csr_subset(x[0], x[1], idx_dev)
+        return SortedCSR(off, rows) if isinstance(x, SortedCSR) else (off, rows)
+    return [x[b] for b in idx_host]
+
+
+def _sub_exclusions(masks, mask: int, sub, exclude, B: int, dev) -> Optional[SortedCSR]:
+    """A group's exclusions (GLOBAL rows) in its sub-catalog's rows: ebt_sub_exclusions."""
+    if exclude is None:
+        return None
+    off, rows = exclude if isinstance(exclude, tuple) else csr_from_lists(exclude, dev)
+    nnz = int(rows.numel())
+    need = int(_lib.load().ebt_sub_exclusions_bytes(B, nnz))
+    if need == 0:
+        raise EbertError(f"exclusion CSR of {B} segments / {nnz} rows cannot be remapped")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    off_out = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    rows_out = torch.empty(max(nnz, 1), dtype=torch.int64, device=dev)
+    call("ebt_sub_exclusions", ptr(masks.table[mask]), masks.words, ptr(sub.rank), sub.n_rows,
+         ptr(off), ptr(rows), B, nnz, ptr(off_out), ptr(rows_out), ptr(ws), need, stream_of(dev))
+    return SortedCSR(off_out, rows_out)
+
+
+def _submit_liked_on_view(parent: Catalog, view: Catalog, k: int, liked, exclude, kprime,
+                          chunk_rows, timer, fuse) -> "PendingTopk":
+    """Liked queries over a sub-catalog: the queries are prepared on the PARENT (liked rows need
+    not be allowed; the image and eps use the parent's u_cat, which the view carries), the first
+    pass runs the prepared entry over the view; score_topk_finish's retry loop completes it."""
+    dev = parent.device
+    lo = liked if isinstance(liked, tuple) else csr_from_lists(liked, dev)
+    if not (isinstance(lo, SortedCSR) and lo.row_min is not None
+            and lo.row_min >= 0 and lo.row_max < parent.n):
+        o0, o1 = int(lo[0][0].item()), int(lo[0][-1].item())
+        seg = lo[1][max(o0, 0):max(o1, 0)]
+        if seg.numel() and bool(((seg < 0) | (seg >= parent.n)).any().item()):
+            raise EbertError(f"liked rows must be in the catalog rows [0, {parent.n})")
+    with region(timer, "prep", dev):
+        qb = prepare_queries(parent, liked=lo)
+    n_cap = _round_up(view.n, 4)
+    k_eff = min(k, view.n)
+    if k_eff > KPRIME_MAX:
+        raise EbertError(f"k={k} > {KPRIME_MAX} over a {view.n}-row sub-catalog is not supported")
+    kp = kprime or default_kprime(view, k_eff)
+    kp = max(_round_up(k_eff, 4), min(_round_up(kp, 4), n_cap, KPRIME_MAX))
+    flags = 0 if fuse else _lib.EBT_FLAG_NO_FUSE
+    s, r, cert = run_pipeline(view, qb, k_eff, kp, exclude, chunk_rows, timer, flags=flags)
+    cert_host = torch.empty(cert.shape, dtype=cert.dtype, pin_memory=True)
+    cert_host.copy_(cert, non_blocking=True)
+    ready = torch.cuda.Event()
+    ready.record(torch.cuda.current_stream(dev))
+    return PendingTopk(view, qb, k, k_eff, kp, exclude, chunk_rows, timer, flags, n_cap, s, r,
+                       cert, cert_host, ready, None)
+
+
+def _submit_routed(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_rows, timer,
+                   fuse, allow) -> Optional[PendingRouted]:
+    """score_topk_submit's routing of a filtered batch over materialised masks
+    (AllowMasks.materialize). Only for a HOST list of mask ids: a device tensor would have to be
+    read back. Returns None -- the batch takes the mask pass as a whole -- when no query's mask
+    has a fresh sub-catalog, or when the arguments are ones the usual path rejects."""
+    from .allow import AllowMasks
+    try:
+        masks, ids = allow
+    except (TypeError, ValueError):
+        return None
+    if not isinstance(masks, AllowMasks) or isinstance(ids, torch.Tensor) or not masks._subs:
+        return None
+    if k < 1 or (queries is None) == (liked is None):
+        return None
+    if queries is not None:
+        if not isinstance(queries, torch.Tensor) or not queries.is_cuda or queries.dim() != 2 \
+                or queries.shape[1] != catalog.d or queries.dtype not in DTYPE_CODE:
+            return None
+        B = int(queries.shape[0])
+    else:
+        B = int(liked[0].numel()) - 1 if isinstance(liked, tuple) else len(liked)
+    if B < 1:
+        return None
+    host = masks.host_ids(ids, B).tolist()
+    groups = {}
+    for b, m in enumerate(host):
+        if m >= 0 and masks.sub_for(catalog, m) is not None:
+            groups.setdefault(m, []).append(b)
+    if not groups:
+        return None
+    dev = catalog.device
+    if isinstance(exclude, tuple) and not isinstance(exclude, SortedCSR):
+        exclude = csr_sorted(*exclude)
+    parts, routes = [], []
+    taken = set()
+    for m, qs in sorted(groups.items()):
+        sub = masks.sub_for(catalog, m)
+        idx = torch.tensor(qs, dtype=torch.int64, device=dev)
+        ex = _sub_exclusions(masks, m, sub, _take(exclude, qs, idx), len(qs), dev)
+        if queries is not None:
+            p = _submit_c(sub.catalog, k, queries.index_select(0, idx), None, ex, kprime,
+                          chunk_rows, timer, fuse)
+        else:
+            p = _submit_liked_on_view(catalog, sub.catalog, k, _take(liked, qs, idx), ex, kprime,
+                                      chunk_rows, timer, fuse)
+        parts.append((idx, p, sub))
+        routes.append((m, list(qs), sub.m))
+        taken.update(qs)
+    rest = [b for b in range(B) if b not in taken]
+    if rest:   # unfiltered queries and masks without a fresh sub-catalog: one sub-batch as before
+        idx = torch.tensor(rest, dtype=torch.int64, device=dev)
+        rest_ids = [host[b] for b in rest]
+        p = _submit_c(catalog, k, queries.index_select(0, idx) if queries is not None else None,
+                      _take(liked, rest, idx), _take(exclude, rest, idx), kprime, chunk_rows,
+                      timer, fuse, (masks, rest_ids) if any(i >= 0 for i in rest_ids) else None)
+        parts.append((idx, p, None))
+    return PendingRouted(catalog, B, k, parts, tuple(routes))
+
+
+def _finish_routed(p: PendingRouted) -> Tuple[torch.Tensor, torch.Tensor]:
+    dev = p.catalog.device
+    out_s = torch.empty((p.B, p.k), dtype=torch.float64, device=dev)
+    out_r = torch.empty((p.B, p.k), dtype=torch.int64, device=dev)
+    for idx, part, sub in p.parts:
+        s, r = score_topk_finish(part)
+        if sub is not None:   # the sub-catalog's rows -> GLOBAL rows (-1 stays -1)
+            r = r.contiguous()
+            call("ebt_sub_rows_to_global", ptr(r), int(r.numel()), ptr(sub.rows), sub.m,
+                 stream_of(dev))
+        out_s[idx] = s
+        out_r[idx] = r
+    return out_s, out_r
+
+
 def score_topk_stages(catalog: Catalog, k: int, queries: Optional[torch.Tensor] = None,
                       liked=None, exclude=None, kprime: Optional[int] = None,
                       chunk_rows: Optional[int] = None, timer: Optional[_lib.Timer] = None,
@@ -621,6 +777,8 @@ def score_topk_stages(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
 
 def score_topk_finish(p) -> Tuple[torch.Tensor, torch.Tensor]:
     """Wait for a submitted batch, run its retries, return (scores f64 [B, k], rows i64 [B, k])."""
+    if isinstance(p, PendingRouted):
+        return _finish_routed(p)
     if isinstance(p, PendingTopkC):
         import ctypes
         if p.allow is not None:
