@@ -10,6 +10,7 @@
 // A mask row is uint32 words[words] (words % 4 == 0): global row r is allowed iff
 // words[r >> 5] >> (r & 31) & 1, and rows >= 32 * words are not allowed.
 #include "common.h"
+#include "internal.h"
 
 namespace ebt {
 
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(MA_THREADS) void allow_set_rows_kernel(
 
 }  // namespace
 
-int64_t allow_words(int64_t n_rows) {
+static int64_t allow_words(int64_t n_rows) {
   if (n_rows < 1) return 0;
   return ((n_rows + 31) / 32 + 3) / 4 * 4;
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "internal.h"
 
 namespace ebt {
 
@@ -101,86 +102,10 @@ std::vector<hipEvent_t>* event_pool() {
   return pools;
 }
 
-// kernels (defined in the other translation units)
-int screen_gemm(const void*, int64_t, const void*, int64_t, int32_t, int32_t, int, const float*,
-                const float*, float*, int64_t, hipStream_t, int64_t cstride = 0);
-int select_topk(const float*, const int64_t*, int64_t, int64_t, int64_t, int64_t, int32_t,
-                int32_t, float*, int64_t*, int64_t, hipStream_t);
-int row_norms(const void*, int, int64_t, int32_t, int64_t, double*, float*, hipStream_t);
-int screen_image(const void*, int, int64_t, int32_t, int64_t, const double*, int, int, void*,
-                 int32_t, hipStream_t, unsigned int* err_max = nullptr);
-int query_dense(const void*, int, int64_t, int32_t, int64_t, double*, hipStream_t);
-int query_liked_sum(const void*, int, int32_t, int64_t, const double*, int64_t, const int64_t*,
-                    const int64_t*, double*, hipStream_t, int64_t row_offset = 0,
-                    int64_t n_local = 0);
-int scale_rows_f64(double*, int64_t, int32_t, const double*, hipStream_t);
-int query_image(const double*, int64_t, int64_t, int32_t, int, const void*, int64_t, int, float,
-                void*, int32_t, float*, float*, hipStream_t);
-int query_prep(const void*, int, int64_t, int64_t, int32_t, int64_t, int, int, float, double*,
-               void*, int32_t, float*, float*, hipStream_t);
-int mask_excluded(float*, int64_t, int64_t, int64_t, int64_t, const int64_t*, const int64_t*,
-                  hipStream_t);
-int mask_allowed(float*, int64_t, int64_t, int64_t, int64_t, const ebt_allow*, hipStream_t);
-int check_allow(const ebt_allow*, int64_t row_end, const char* who);
-int rescore(const double*, int64_t, int32_t, const void*, int, int64_t, const double*, int64_t,
-            const float*, const int64_t*, int32_t, int32_t, int64_t, const float*, const double*,
-            double*, int64_t*, int32_t*, hipStream_t, const int*, int, unsigned long long*,
-            int64_t list_base = 0, const float* theta = nullptr,
-            const int64_t* excl_off = nullptr, const int64_t* excl_rows = nullptr,
-            const ShardPackOut* pack = nullptr);
-int screen_gemm_filter(const void*, int64_t, const void*, int64_t, int32_t, int32_t, int,
-                       const float*, const float*, const float*, uint64_t*, int64_t, int,
-                       uint8_t*, int64_t, int*, int64_t, hipStream_t);
-int64_t filter_group_rows(int64_t);
-int64_t filter_split_rows(int64_t B_pad, int64_t n_rows);
-
-int spec_threshold(const float*, int64_t, int64_t, int64_t, int, const float*, const float*, float*,
-                   int*, int, hipStream_t);
-int kth_threshold(const float*, int64_t, int64_t, int64_t, int, const float*, float*,
-                  hipStream_t);
-int pool_kth(const float*, int64_t, int64_t, int64_t, int, int, float*, hipStream_t,
-             float* fv = nullptr, int64_t* fi = nullptr, int kprime = 0, int* ovf = nullptr,
-             const float* lead_s = nullptr, int64_t ld_lead = 0, int lead = 0,
-             uint64_t* cand = nullptr, int64_t ld_cand = 0, int slots = 0,
-             uint8_t* counts = nullptr, int64_t ld_counts = 0, int gj = 0,
-             int64_t rstride = 0);
-int spec_given_init(const float*, int64_t, int64_t, float*, float*, int64_t*, int, int*,
-                    hipStream_t, const float* lead_s = nullptr, int64_t ld_lead = 0, int lead = 0,
-                    uint64_t* cand = nullptr, int64_t ld_cand = 0, int slots = 0,
-                    uint8_t* counts = nullptr, int64_t ld_counts = 0);
-int screen_gemm_pool(const void*, int64_t, const void*, int64_t, int32_t, int32_t, int,
-                     const float*, const float*, int64_t, float*, int64_t, hipStream_t,
-                     int64_t lead = 0, float* lead_scores = nullptr, int64_t ld_lead = 0);
-int64_t gemm_cus();
-int merge_segment(float*, int64_t*, int64_t, int, const uint64_t*, int64_t, int, const uint8_t*,
-                  int64_t, int64_t, int64_t, const int64_t*, const int64_t*, int*, hipStream_t,
-                  double expect_hits = 0.0);
-bool merge_wave_fits(int);
-int merge_wave_capacity();
-int merge_block_capacity(int);
-int64_t merge_wave_max_groups();
-int64_t merge_block_max_groups(int);
-int merge_segment_wave(float*, int64_t*, int64_t, int, int, const uint64_t*, int64_t, int,
-                       const uint8_t*, int64_t, int64_t, int64_t, const int64_t*, const int64_t*,
-                       int*, hipStream_t, const float* veps = nullptr,
-                       const float* vspec = nullptr, float* fout = nullptr, int fw = 0,
-                       const float* feps = nullptr, float* tout = nullptr,
-                       const float* tin = nullptr, const float* teps = nullptr,
-                       int64_t B_pad = 0);
-int pilot_topk(const float*, int64_t, int64_t, int, int64_t, int, int, float*, int64_t*,
-               hipStream_t);
 constexpr int64_t PILOT_ROWS = 1024;  // = WMERGE_H (select_topk.hip)
-int merge_topk(const double*, const int64_t*, int32_t, int64_t, int32_t, double*, int64_t*,
-               hipStream_t);
-int screen_exact(const double*, int64_t, int32_t, const void*, int, int64_t, const double*, int64_t,
-                 float*, int64_t, hipStream_t);
-int export_list(int64_t*, int64_t, int32_t, int64_t, const int*, const float*, int32_t*, float*,
-                hipStream_t);
-int rescore_owned(const double*, int64_t, int32_t, const void*, int, int64_t, const double*,
-                  int64_t, int64_t, const float*, const int64_t*, int32_t, int32_t, const float*,
-                  double*, hipStream_t);
-int finalize_topk(const float*, const int64_t*, const double*, int64_t, int32_t, int32_t, int64_t,
-                  const float*, const int32_t*, double*, int64_t*, int32_t*, hipStream_t);
+
+// The host-only types of this file are file-local (internal.h: the linkage rule)
+namespace {
 
 // EBT_FLAG_EXACT screening operands (the float64 catalog path), null for the MFMA screen
 struct ExactScreen {
@@ -276,6 +201,8 @@ struct StageScope {
   }
 };
 
+}  // namespace
+
 // A stage that is exactly one kernel launch (the filter GEMM's, the roofline's dominant kernel):
 // its event pair is handed to the launch (take_launch_events -> hipExtLaunchKernelGGL), which
 // binds the events to the dispatch -- no marker packets between the launches of the timed
@@ -296,6 +223,8 @@ static bool timer_markers() {
   }();
   return on;
 }
+namespace {
+
 struct KernelStage {
   Timer* t;
   int stage;
@@ -351,6 +280,8 @@ struct WsLayout {
   size_t off_s, off_segv, off_segi, off_chv, off_chi, off_fv, off_fi, off_cand, off_counts,
       off_thr, off_ovf, off_eps, off_tspec, off_lead, bytes;
 };
+
+}  // namespace
 
 constexpr int SPEC_KPRIME_MAX = 2048;
 
@@ -446,7 +377,6 @@ static bool spec_params(int64_t B_pad, int64_t n_rows, int32_t kprime, int64_t* 
   return true;
 }
 
-static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // ebt_spec_lead: 1 = the speculative screen's lead tiles (default; EBT_SPEC_LEAD=0 in the
 // environment starts the process without them)
@@ -685,7 +615,7 @@ static int head_topk(const WsLayout& L, char* ws, const void* qimg, const float*
   return EBT_OK;
 }
 
-// The rescore of the row-sharded step (driver.hip): the shard's list holds GLOBAL rows
+// The rescore of the row-sharded step (sharded.hip): the shard's list holds GLOBAL rows
 // (list_base = row_offset: no local-rows pass), and the certificate also takes ebt_certify_cut's
 // tests (an overflowed fused list, a caller's threshold above the floor's cut) -- two launches
 // fewer per step. Timed and row-counted as ebt_rescore.
@@ -888,6 +818,7 @@ int ebt_spec_lead(int on) {
 }  // extern "C"
 
 namespace ebt {
+namespace {
 
 // What the rescore needs from the screen: the eps the certificate uses (the caller's, or the
 // exact screen's constant) and the fused screen's overflow flags (null when not fused).
@@ -940,6 +871,8 @@ struct PipeArgs {
   // only: the entry sets EBT_FLAG_NO_FUSE), null = unfiltered
   const ebt_allow* allow = nullptr;
 };
+
+}  // namespace
 
 static int check_pipe(const PipeArgs& a, const char* who) {
   const bool exact = a.flags & EBT_FLAG_EXACT;
@@ -1445,7 +1378,7 @@ int ebt_cosine_screen_at_lead(const double* q64, const void* qimg, const float* 
 
 namespace ebt {
 // The sharded step's screen at the shared threshold without ebt_cosine_screen_at_lead's export
-// launch (driver.hip): the list keeps LOCAL rows (the sharded rescore reads them with list base
+// launch (sharded.hip): the list keeps LOCAL rows (the sharded rescore reads them with list base
 // 0), and the screen's own overflow flags and eps stay where the pipeline wrote them (*ovf_dev,
 // *eps_dev point into the workspace / the prepared queries).
 int screen_at_local(const double* q64, const void* qimg, const float* qscale, const float* eps,

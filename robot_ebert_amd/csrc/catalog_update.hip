@@ -33,7 +33,14 @@
 // edited matrix. Every source is >= n' and every destination < n': no move reads what another
 // writes. The kernel is bound by memory latency: a lane issues the loads of up to MOVE_AHEAD
 // 16-byte chunks before their stores.
+//
+// The catalog lifecycle entries of the C ABI (ebt_catalog_state_bytes, _init, _init_reserved,
+// _update_rows, _append_rows, _remove_plan, _remove_rows) follow their kernels, at the end.
+#include <cmath>
+#include <vector>
+
 #include "common.h"
+#include "driver.h"
 
 namespace ebt {
 
@@ -274,9 +281,9 @@ __global__ __launch_bounds__(256) void catalog_update_kernel(const UpdArgs a) {
   }
 }
 
-// Host side: every argument was checked by the caller (driver.hip); `rows` is a device array or
+// Host side: every argument was checked by the caller (below); `rows` is a device array or
 // NULL (append: local rows row0 .. row0 + m - 1). img == NULL when the matrix is its own image.
-int catalog_update(void* data, int dtype, int32_t d, int64_t ld, const int64_t* rows,
+static int catalog_update(void* data, int dtype, int32_t d, int64_t ld, const int64_t* rows,
                    int64_t row_offset, int64_t row0, int64_t m, const void* src, int src_dtype,
                    int64_t ld_src, double* gnorm, float* inv32, void* img, int img_dtype,
                    int32_t ld_img, int normalize, unsigned int* err_max, hipStream_t st) {
@@ -379,9 +386,9 @@ __global__ __launch_bounds__(256) void catalog_move_kernel(const MoveArgs a) {
   }
 }
 
-// Host side: every argument was checked by the caller (driver.hip); `moves` is a device array of
+// Host side: every argument was checked by the caller (below); `moves` is a device array of
 // p (src, dst) pairs of LOCAL rows. img == NULL when the matrix is its own image.
-int catalog_move(void* data, int dtype, int32_t d, int64_t ld, const int64_t* moves, int64_t p,
+static int catalog_move(void* data, int dtype, int32_t d, int64_t ld, const int64_t* moves, int64_t p,
                  int64_t n_new, int64_t n_old, double* gnorm, float* inv32, void* img,
                  int32_t ld_img, hipStream_t st) {
   if (!data || !gnorm || !inv32 || p < 0 || (p > 0 && !moves) || d <= 0 || ld < d || dtype < 0 ||
@@ -407,4 +414,363 @@ int catalog_move(void* data, int dtype, int32_t d, int64_t ld, const int64_t* mo
   return launch_check("catalog_move_kernel");
 }
 
+namespace {
+
+// The catalog state for n_cap rows: gnorm64 [n_cap] at 0, inv32 [round_up(n_cap, 128)], the
+// image [n_cap][d_pad] unless the matrix is its own image (alias), and for a non-native catalog
+// the slot of the image's measured rounding error. bytes == 0: refused sizes.
+struct StateLayout {
+  size_t inv32, img, err, bytes;
+  bool native, alias;
+};
+StateLayout state_layout(const void* data, int dtype, int64_t n_cap, int32_t d, int64_t ld) {
+  StateLayout L{};
+  if (n_cap < 1 || d < 1 || ld < d || dtype < 0 || dtype > 3) return L;
+  L.native = dtype == EBT_F16 || dtype == EBT_BF16;
+  L.alias = L.native && d % 64 == 0 && ld % 64 == 0 && ((uintptr_t)data & 15) == 0;
+  size_t o = 0;
+  carve(o, (size_t)n_cap * 8);
+  L.inv32 = carve(o, (size_t)round_up(n_cap, 128) * 4);
+  L.img = carve(o, L.alias ? 0 : (size_t)n_cap * round_up(d, 64) * 2);
+  L.err = carve(o, L.native ? 0 : 4);
+  L.bytes = o;
+  return L;
+}
+
+constexpr int ONE_F32_BITS = 0x3f800000;
+
+// the image's measured rounding error read back from its slot (one stream sync)
+int read_u_cat(const unsigned int* d_err, hipStream_t st, float* u_cat) {
+  float u = 0.0f;
+  int rc = hip_check(hipMemcpyAsync(&u, d_err, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+  if (!rc) rc = hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (!rc) *u_cat = std::isfinite(u) && u >= 0.0f ? u : 1.0f / 2048.0f;
+  return rc;
+}
+
+// m GLOBAL rows of the catalog rows [row_offset, row_offset + n), strictly ascending; else the
+// error is set
+bool rows_ascending(const char* who, const int64_t* rows, int64_t m, int64_t row_offset,
+                    int64_t n) {
+  for (int64_t i = 0; i < m; ++i) {
+    if (rows[i] < row_offset || rows[i] >= row_offset + n) {
+      set_error("%s: rows[%lld] = %lld is not in [%lld, %lld)", who, (long long)i,
+                (long long)rows[i], (long long)row_offset, (long long)(row_offset + n));
+      return false;
+    }
+    if (i > 0 && rows[i] <= rows[i - 1]) {
+      set_error("%s: rows must be strictly ascending (rows[%lld] = %lld after %lld)", who,
+                (long long)i, (long long)rows[i], (long long)rows[i - 1]);
+      return false;
+    }
+  }
+  return true;
+}
+
+}  // namespace
+
 }  // namespace ebt
+
+using namespace ebt;
+
+extern "C" {
+
+size_t ebt_catalog_state_bytes(const void* data, int dtype, int64_t n, int32_t d, int64_t ld) {
+  return state_layout(data, dtype, n, d, ld).bytes;
+}
+
+// ebt_catalog_init (n_cap == n) and ebt_catalog_init_reserved: the state is laid out for n_cap
+// rows and initialised for the first n
+static int catalog_init_cap(const char* who, ebt_catalog* cat, const void* data, int dtype,
+                            int64_t n, int64_t n_cap, int32_t d, int64_t ld, int64_t row_offset,
+                            void* state, size_t state_bytes, void* stream) {
+  const StateLayout SL = n_cap >= n ? state_layout(data, dtype, n_cap, d, ld) : StateLayout{};
+  const size_t need = SL.bytes;
+  if (!cat || !data || !state || need == 0 || n < 1 || row_offset < 0) {
+    set_error("%s: bad arguments (n=%lld n_cap=%lld d=%d ld=%lld dtype=%d)", who, (long long)n,
+              (long long)n_cap, d, (long long)ld, dtype);
+    return EBT_EINVAL;
+  }
+  if (state_bytes < need) {
+    set_error("%s: state %zu < %zu bytes", who, state_bytes, need);
+    return EBT_ENOMEM;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ebt_catalog c{};
+  c.data = data;
+  c.dtype = dtype;
+  c.d = d;
+  c.n = n;
+  c.ld = ld;
+  c.row_offset = row_offset;
+  c.d_pad = (int32_t)round_up(d, 64);
+  char* s = (char*)state;
+  c.gnorm64 = (double*)s;
+  c.inv32 = (float*)(s + SL.inv32);
+  char* img = s + SL.img;
+  int rc = EBT_OK;
+  if (round_up(n_cap, 128) > n)  // inv32 past the rows: 1.0f
+    rc = hip_check(hipMemsetD32Async((hipDeviceptr_t)(c.inv32 + n), ONE_F32_BITS,
+                                     (size_t)(round_up(n_cap, 128) - n), st), "hipMemsetD32Async");
+  if (!rc) rc = ebt_row_norms(data, dtype, n, d, ld, c.gnorm64, c.inv32, st);
+  if (rc) return rc;
+  if (SL.native) {
+    c.img_dtype = dtype;
+    c.u_cat = 0.0f;
+    c.cscale = c.inv32;
+    c.native = 1;
+    if (SL.alias) {
+      c.image = data;  // the matrix itself is the MFMA operand
+      c.ld_img = (int32_t)ld;
+    } else {
+      c.ld_img = c.d_pad;
+      c.image = img;
+      rc = ebt_screen_image(data, dtype, n, d, ld, c.gnorm64, 0, c.img_dtype, img, c.ld_img, st);
+    }
+  } else {
+    // f16 image of the normalised rows. u_cat = the largest ||image row - row / gnorm||_2 over
+    // the rows, measured by the image kernel (rounded up to a float; rows with non-finite
+    // values left out) -- ~0.4 x the unit round-off 2^-11 that bounds it a priori, so the
+    // certificate's eps band (and the rows the rescore gathers) is about half as wide; one
+    // stream sync to read it back, once per catalog
+    c.img_dtype = EBT_F16;
+    c.cscale = nullptr;
+    c.native = 0;
+    c.ld_img = c.d_pad;
+    c.image = img;
+    unsigned int* d_err = (unsigned int*)(s + SL.err);
+    rc = hip_check(hipMemsetAsync(d_err, 0, 4, st), "hipMemsetAsync");
+    if (!rc)
+      rc = screen_image(data, dtype, n, d, ld, c.gnorm64, 1, c.img_dtype, img, c.ld_img, st,
+                        d_err);
+    if (!rc) rc = read_u_cat(d_err, st, &c.u_cat);
+  }
+  if (rc) return rc;
+  *cat = c;
+  return EBT_OK;
+}
+
+int ebt_catalog_init(ebt_catalog* cat, const void* data, int dtype, int64_t n, int32_t d,
+                     int64_t ld, int64_t row_offset, void* state, size_t state_bytes,
+                     void* stream) {
+  return catalog_init_cap("ebt_catalog_init", cat, data, dtype, n, n, d, ld, row_offset, state,
+                          state_bytes, stream);
+}
+
+int ebt_catalog_init_reserved(ebt_catalog* cat, const void* data, int dtype, int64_t n,
+                              int64_t n_cap, int32_t d, int64_t ld, int64_t row_offset,
+                              void* state, size_t state_bytes, void* stream) {
+  return catalog_init_cap("ebt_catalog_init_reserved", cat, data, dtype, n, n_cap, d, ld,
+                          row_offset, state, state_bytes, stream);
+}
+
+// ---- live updates (0.4.0): catalog_update_kernel ------------------------------------------------
+size_t ebt_catalog_update_bytes(int64_t m) { return m > 0 ? align_up((size_t)m * 8) : 0; }
+
+namespace {
+
+// Where catalog_init_cap put the parts of a state laid out for n_cap rows
+struct StateParts {
+  double* gnorm;
+  float* inv32;
+  void* img;              // NULL: the matrix is its own image
+  unsigned int* err;      // NULL for a native catalog
+};
+
+// Host checks shared by the two update entries: *cat is a catalog that catalog_init_cap laid out
+// in `state` for n_cap rows, and the source is usable
+int update_check(const char* who, const ebt_catalog* cat, void* state, size_t state_bytes,
+                 int64_t n_cap, int64_t m, const void* src, int src_dtype, int64_t ld_src,
+                 StateParts* out) {
+  if (!valid_catalog(cat) || !state || cat->dtype < 0 || cat->dtype > 3 || cat->row_offset < 0) {
+    set_error("%s: bad catalog or state", who);
+    return EBT_EINVAL;
+  }
+  const ebt_catalog& c = *cat;
+  if (m < 0 || src_dtype < 0 || src_dtype > 3 || (m > 0 && (!src || ld_src < c.d))) {
+    set_error("%s: bad source (m=%lld src_dtype=%d ld_src=%lld d=%d)", who, (long long)m,
+              src_dtype, (long long)ld_src, c.d);
+    return EBT_EINVAL;
+  }
+  const StateLayout SL =
+      n_cap >= c.n ? state_layout(c.data, c.dtype, n_cap, c.d, c.ld) : StateLayout{};
+  const size_t need = SL.bytes;
+  if (need == 0 || state_bytes < need) {
+    set_error("%s: n_cap %lld (n %lld) needs a state of %zu bytes, got %zu", who,
+              (long long)n_cap, (long long)c.n, need, state_bytes);
+    return EBT_EINVAL;
+  }
+  const bool native = SL.native, alias = SL.alias;
+  char* s = (char*)state;
+  char* img = s + SL.img;
+  StateParts P;
+  P.gnorm = (double*)s;
+  P.inv32 = (float*)(s + SL.inv32);
+  P.img = alias ? nullptr : img;
+  P.err = native ? nullptr : (unsigned int*)(s + SL.err);
+  const void* want_image = alias ? c.data : (const void*)img;
+  const int32_t want_ld_img = alias ? (int32_t)c.ld : c.d_pad;
+  const int want_img_dtype = native ? c.dtype : EBT_F16;
+  if (c.gnorm64 != P.gnorm || c.inv32 != P.inv32 || c.image != want_image ||
+      c.ld_img != want_ld_img || c.img_dtype != want_img_dtype || c.native != (native ? 1 : 0) ||
+      c.cscale != (native ? P.inv32 : nullptr) || c.d_pad != (int32_t)round_up(c.d, 64)) {
+    set_error("%s: the catalog is not laid out in this state for n_cap = %lld (a catalog of "
+              "ebt_catalog_init / _reserved with the same capacity is required)", who,
+              (long long)n_cap);
+    return EBT_EINVAL;
+  }
+  *out = P;
+  return EBT_OK;
+}
+
+// the kernel, then for a non-native catalog the error slot read back into cat->u_cat
+int update_launch(ebt_catalog* cat, const StateParts& P, const int64_t* d_rows, int64_t row0,
+                  int64_t m, const void* src, int src_dtype, int64_t ld_src, hipStream_t st) {
+  const ebt_catalog& c = *cat;
+  int rc = catalog_update(const_cast<void*>(c.data), c.dtype, c.d, c.ld, d_rows, c.row_offset,
+                          row0, m, src, src_dtype, ld_src, P.gnorm, P.inv32, P.img, c.img_dtype,
+                          c.ld_img, c.native ? 0 : 1, P.err, st);
+  if (rc || !P.err) return rc;
+  return read_u_cat(P.err, st, &cat->u_cat);
+}
+
+}  // namespace
+
+int ebt_catalog_update_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
+                            const int64_t* rows, int64_t m, const void* src, int src_dtype,
+                            int64_t ld_src, void* ws, size_t ws_bytes, void* stream) {
+  StateParts P;
+  int rc = update_check("ebt_catalog_update_rows", cat, state, state_bytes, n_cap, m, src,
+                        src_dtype, ld_src, &P);
+  if (rc) return rc;
+  if (m == 0) return EBT_OK;
+  const ebt_catalog& c = *cat;
+  if (!rows) {
+    set_error("ebt_catalog_update_rows: rows is NULL");
+    return EBT_EINVAL;
+  }
+  if (!rows_ascending("ebt_catalog_update_rows", rows, m, c.row_offset, c.n)) return EBT_EINVAL;
+  const size_t need = ebt_catalog_update_bytes(m);
+  if (!ws || ws_bytes < need) {
+    set_error("ebt_catalog_update_rows: workspace %zu < %zu bytes", ws ? ws_bytes : (size_t)0,
+              need);
+    return EBT_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  rc = hip_check(hipMemcpyAsync(ws, rows, (size_t)m * 8, hipMemcpyHostToDevice, st),
+                 "hipMemcpyAsync");
+  if (rc) return rc;
+  return update_launch(cat, P, (const int64_t*)ws, 0, m, src, src_dtype, ld_src, st);
+}
+
+int ebt_catalog_append_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
+                            int64_t m, const void* src, int src_dtype, int64_t ld_src,
+                            void* stream) {
+  StateParts P;
+  int rc = update_check("ebt_catalog_append_rows", cat, state, state_bytes, n_cap, m, src,
+                        src_dtype, ld_src, &P);
+  if (rc) return rc;
+  if (m > n_cap - cat->n) {
+    set_error("ebt_catalog_append_rows: n %lld + m %lld > n_cap %lld", (long long)cat->n,
+              (long long)m, (long long)n_cap);
+    return EBT_EINVAL;
+  }
+  if (m == 0) return EBT_OK;
+  rc = update_launch(cat, P, nullptr, cat->n, m, src, src_dtype, ld_src, (hipStream_t)stream);
+  if (rc) return rc;
+  cat->n += m;
+  return EBT_OK;
+}
+
+// ---- removal (0.5.0): catalog_move_kernel -----------------------------------------------------
+size_t ebt_catalog_remove_bytes(int64_t m) { return m > 0 ? align_up((size_t)m * 16) : 0; }
+
+namespace {
+
+// The rule of ebert.h: with n' = n - m, the removed rows below n' (the holes, ascending) receive
+// the rows of [n', n) that are not removed (the survivors, ascending). `rows` is checked; the p
+// moves go to from / to (GLOBAL rows) when given. Returns p, or -1 with the error set.
+int64_t remove_plan(const char* who, int64_t n, int64_t row_offset, const int64_t* rows,
+                    int64_t m, int64_t* from, int64_t* to) {
+  if (n < 1 || row_offset < 0 || m < 0 || (m > 0 && !rows) || ((from == nullptr) != (to == nullptr))) {
+    set_error("%s: bad arguments (n=%lld row_offset=%lld m=%lld; from / to both or neither)", who,
+              (long long)n, (long long)row_offset, (long long)m);
+    return -1;
+  }
+  if (!rows_ascending(who, rows, m, row_offset, n)) return -1;
+  if (m >= n) {
+    set_error("%s: cannot remove every row (m %lld >= n %lld)", who, (long long)m, (long long)n);
+    return -1;
+  }
+  const int64_t n_new = n - m;
+  int64_t p = 0;
+  while (p < m && rows[p] - row_offset < n_new) ++p;   // the holes are rows[0 .. p)
+  // rows[p .. m) are the removed rows of [n', n): the survivors are the others, p of them
+  int64_t t = p, s = n_new;
+  for (int64_t i = 0; i < p; ++i, ++s) {
+    while (t < m && rows[t] - row_offset == s) ++t, ++s;
+    if (from) {
+      from[i] = row_offset + s;
+      to[i] = rows[i];
+    }
+  }
+  return p;
+}
+
+}  // namespace
+
+int64_t ebt_catalog_remove_plan(int64_t n, int64_t row_offset, const int64_t* rows, int64_t m,
+                                int64_t* from, int64_t* to) {
+  return remove_plan("ebt_catalog_remove_plan", n, row_offset, rows, m, from, to);
+}
+
+int ebt_catalog_remove_rows(ebt_catalog* cat, void* state, size_t state_bytes, int64_t n_cap,
+                            const int64_t* rows, int64_t m, void* ws, size_t ws_bytes,
+                            void* stream) {
+  const char* who = "ebt_catalog_remove_rows";
+  StateParts P;
+  int rc = update_check(who, cat, state, state_bytes, n_cap, 0, nullptr, 0, 0, &P);
+  if (rc) return rc;
+  if (m < 0) {
+    set_error("%s: m = %lld", who, (long long)m);
+    return EBT_EINVAL;
+  }
+  if (m == 0) return EBT_OK;
+  if (!rows) {
+    set_error("%s: rows is NULL", who);
+    return EBT_EINVAL;
+  }
+  const ebt_catalog& c = *cat;
+  std::vector<int64_t> from((size_t)m), to((size_t)m);
+  const int64_t p = remove_plan(who, c.n, c.row_offset, rows, m, from.data(), to.data());
+  if (p < 0) return EBT_EINVAL;
+  const size_t need = ebt_catalog_remove_bytes(m);
+  if (!ws || ws_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", who, ws ? ws_bytes : (size_t)0, need);
+    return EBT_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n_new = c.n - m;
+  if (p > 0) {
+    std::vector<int64_t> pairs((size_t)p * 2);   // LOCAL (src, dst)
+    for (int64_t i = 0; i < p; ++i) {
+      pairs[2 * i] = from[i] - c.row_offset;
+      pairs[2 * i + 1] = to[i] - c.row_offset;
+    }
+    // a copy from pageable memory has left the host buffer when the call returns
+    rc = hip_check(hipMemcpyAsync(ws, pairs.data(), (size_t)p * 16, hipMemcpyHostToDevice, st),
+                   "hipMemcpyAsync");
+    if (!rc)
+      rc = catalog_move(const_cast<void*>(c.data), c.dtype, c.d, c.ld, (const int64_t*)ws, p,
+                        n_new, c.n, P.gnorm, P.inv32, P.img, c.ld_img, st);
+    if (rc) return rc;
+  }
+  // after the moves, which read inv32 in this range: rows past n' hold 1.0f again
+  rc = hip_check(hipMemsetD32Async((hipDeviceptr_t)(P.inv32 + n_new), ONE_F32_BITS, (size_t)m, st),
+                 "hipMemsetD32Async");
+  if (rc) return rc;
+  cat->n = n_new;
+  return EBT_OK;
+}
+
+}  // extern "C"

@@ -266,6 +266,14 @@ __device__ __forceinline__ double guard_norm(double nrm) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Workspace regions are 256-byte aligned. carve: the region's offset; `o` moves past it
+inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+inline size_t carve(size_t& o, size_t bytes) {
+  const size_t at = o;
+  o = align_up(o + bytes);
+  return at;
+}
+
 // ebt_shard_pack's buffer (0.3.2): u32 start[B], u32 len[B] (query b's entries are
 // [start[b], start[b] + len[b]); the starts are prefix sums of the lengths in query order: the
 // sharded rescore writes len[b], shard_pack_lens places the ranges), u32 block

@@ -31,8 +31,6 @@ constexpr int XS_LDS = 4096;      // rows sorted in LDS at once (32 KiB)
 constexpr int XS_ITEMS = 8;       // merge outputs per thread and round
 constexpr int XS_COPY_BLOCKS = 64;
 
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 __device__ __forceinline__ int64_t clamp_off(int64_t x, int64_t nnz) {
   return x < 0 ? 0 : (x > nnz ? nnz : x);
 }
@@ -176,7 +174,7 @@ extern "C" {
 size_t ebt_sort_exclusions_bytes(int64_t B, int64_t nnz) {
   // (B: one workgroup per segment, the grid's threads within 32 bits)
   if (B < 1 || nnz < 0 || nnz > 0x7fffffffLL || B > (1LL << 24)) return 0;
-  return al256((size_t)(nnz > 0 ? nnz : 1) * 8);
+  return align_up((size_t)(nnz > 0 ? nnz : 1) * 8);
 }
 
 int ebt_sort_exclusions(const int64_t* off, const int64_t* rows_in, int64_t* rows_out, int64_t B,

@@ -23,6 +23,7 @@
 // Round 6: hand-written, replacing one radix sort per query through the CUB-compatible API.
 // A rare path (no caller of the reference asks for more than k = 100): plain, not tuned.
 #include "common.h"
+#include "internal.h"
 
 namespace ebt {
 
@@ -31,8 +32,6 @@ namespace {
 constexpr int LT = 64, LK = 16;
 constexpr int64_t LARGE_KEY_BUDGET = 1LL << 30;  // key bytes of one group of queries
 constexpr int64_t LARGE_GROUP_MAX = 64;
-
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ uint64_t score_key(double v) {
   if (v != v) return 0ull;  // NaN: not a candidate (the key of an excluded row)
@@ -234,7 +233,7 @@ size_t large_topk_bytes(int64_t B, int64_t n, int64_t* Bg_out) {
   Bg = Bg > LARGE_GROUP_MAX ? LARGE_GROUP_MAX : Bg;
   Bg = Bg > B ? B : Bg;
   if (Bg_out) *Bg_out = Bg;
-  return 2 * (al256((size_t)Bg * n * 8) + al256((size_t)Bg * n * 4));
+  return 2 * (align_up((size_t)Bg * n * 8) + align_up((size_t)Bg * n * 4));
 }
 
 int large_topk(const double* q64, int64_t B, int32_t d, const void* cat, int dtype, int64_t ld,
@@ -250,11 +249,11 @@ int large_topk(const double* q64, int64_t B, int32_t d, const void* cat, int dty
   }
   char* w = (char*)ws;
   uint64_t* k0 = (uint64_t*)w;
-  w += al256((size_t)Bg * n * 8);
+  w += align_up((size_t)Bg * n * 8);
   int32_t* i0 = (int32_t*)w;
-  w += al256((size_t)Bg * n * 4);
+  w += align_up((size_t)Bg * n * 4);
   uint64_t* k1 = (uint64_t*)w;
-  w += al256((size_t)Bg * n * 8);
+  w += align_up((size_t)Bg * n * 8);
   int32_t* i1 = (int32_t*)w;
   int rc = EBT_OK;
   for (int64_t b0 = 0; b0 < B; b0 += Bg) {

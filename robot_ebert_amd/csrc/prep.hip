@@ -12,6 +12,7 @@
 //  * query_image    -- the query's MFMA operand, its epilogue scale and the certification bound.
 //  * mask_excluded  -- rated movies are not candidates (lib.py:48,55).
 #include "common.h"
+#include "internal.h"
 
 namespace ebt {
 

@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "internal.h"
 
 namespace ebt {
 
@@ -783,7 +784,7 @@ extern "C" int ebt_wave_sum_check(const double* in, int64_t n_waves, double* out
   return launch_check("wave_sum_check_kernel");
 }
 
-size_t rescore_lds_bytes(int d, int kprime) {
+static size_t rescore_lds_bytes(int d, int kprime) {
   const int kpp = next_pow2_h(kprime);
   return 8 * (size_t)((d + 1) & ~1) + 20 * (size_t)kpp;
 }
@@ -969,7 +970,7 @@ __device__ __forceinline__ bool mt_before(double xs, int64_t xr, double es, int6
   return xs > es || (xs == es && xr < er);
 }
 
-size_t merge_corank_lds(int R, int P) {
+static size_t merge_corank_lds(int R, int P) {
   return (size_t)P * 16 + RTHREADS * 16 + (((size_t)(2 * R + 1) * 4 + 15) & ~(size_t)15);
 }
 
@@ -1235,7 +1236,7 @@ __host__ __device__ inline int merge_packed_room(int R, int k) {
   const int64_t all = (int64_t)R * k, room = 2LL * k + 256;
   return (int)(all < room ? all : room);
 }
-size_t merge_packed_lds(int R, int k) {
+static size_t merge_packed_lds(int R, int k) {
   const size_t n = (size_t)merge_packed_room(R, k);
   return n * 8 + ((n * 4 + 15) & ~(size_t)15) + (((size_t)(3 * R + 1) * 4 + 15) & ~(size_t)15);
 }
@@ -1555,7 +1556,7 @@ int shard_pack_lens(const double* scores, const int64_t* rows, int64_t B, int32_
   return launch_check("shard_pack_lens_kernel");
 }
 
-int64_t shard_list_width(int32_t k, int32_t world) {
+static int64_t shard_list_width(int32_t k, int32_t world) {
   const int64_t w = (3 * (int64_t)k + 2 * world - 1) / (2 * world) + 8;  // ceil(1.5 k / R) + 8
   return w < k ? w : k;
 }
@@ -2026,10 +2027,6 @@ __global__ void certify_cut_kernel(int32_t* __restrict__ cert, const int32_t* __
 
 }  // namespace ebt
 
-namespace ebt {
-int union_floor(const float* gathered, int32_t R, int64_t B, int32_t ld, int32_t k,
-                double* t_floor, hipStream_t stream, uint32_t* zero2);
-}
 extern "C" int ebt_union_floor(const float* gathered, int32_t R, int64_t B, int32_t ld, int32_t k,
                                double* t_floor, void* stream) {
   return ebt::union_floor(gathered, R, B, ld, k, t_floor, (hipStream_t)stream, nullptr);

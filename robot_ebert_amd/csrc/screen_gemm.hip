@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "internal.h"
 
 namespace ebt {
 
@@ -1472,8 +1473,6 @@ static int launch_gemm(const void* qimg, int64_t B_pad, const void* cimg, int64_
                        n_ctiles, d_pad / GBK, qscale, cscale, e);
   return launch_check("screen_gemm_kernel");
 }
-
-int64_t filter_group_rows(int64_t B_pad);
 
 static int check_gemm_args(const char* who, const void* qimg, int64_t B_pad, const void* cimg,
                            int64_t n_rows, int32_t d_pad, int32_t ld_img, int img_dtype,

@@ -16,6 +16,7 @@
 // Composites are unique (indices are), so the result is deterministic: exactly the k' largest
 // (value, -index) pairs. NaN and -inf (masked / excluded) entries have key 0 and never enter.
 #include "common.h"
+#include "internal.h"
 
 namespace ebt {
 
@@ -425,7 +426,7 @@ __global__ __launch_bounds__(STHREADS, EBT_SEL_WGS) void select_topk_kernel(
   }
 }
 
-size_t select_lds_bytes(int kprime) { return sel_layout(kprime).bytes; }
+static size_t select_lds_bytes(int kprime) { return sel_layout(kprime).bytes; }
 
 // tiles in flight per workgroup: two for a plain score row; one when int64 row ids travel with
 // the values (three times the registers per value)
@@ -712,7 +713,7 @@ __global__ __launch_bounds__(STHREADS) void merge_segment_kernel(
   }
 }
 
-size_t merge_lds_dyn() {
+static size_t merge_lds_dyn() {
   static size_t dyn = [] {
     hipFuncAttributes a{};
     size_t st = 1024;  // a safe static estimate if the attributes cannot be read
@@ -770,8 +771,6 @@ static int merge_segment_part(float* fv, int64_t* fi, int64_t B, int kprime,
                      counts, ld_counts, (int)n_groups, P_max, row_offset, eo, er, ovf, 0, B);
   return launch_check("merge_segment_kernel");
 }
-
-int64_t merge_block_max_groups(int kprime);
 
 // More groups than one block merge can index (its u16 group positions share the LDS with the
 // P_max entries): merge them in consecutive parts of whole 16-group blocks. Each part merges

@@ -43,7 +43,7 @@ SAMPLE_TILES_MAX = 64   # per shard, as the single-GPU speculative screen (api.h
 # its threshold (list k-th - 2 eps) soon enough, and the shared threshold's uniform hits cost
 # as much as they save (round 5, tools/rank_sim_capi.py replays of C3, two runs each: 4 ranks
 # 2.689 vs 2.734 ms per step with the shared threshold, 2 ranks 5.251 vs 5.214 ms; round 3's
-# shard_sim: 8 ranks -3 %). driver.hip EBT_SH_SHARED_MAX is the same limit.
+# shard_sim: 8 ranks -3 %). sharded.hip EBT_SH_SHARED_MAX is the same limit.
 SHARED_MAX_SHARD_ROWS = 300_000
 
 
@@ -298,7 +298,7 @@ def sample_send_width(kp_glob: int, tiles: int, world: int, n_global: int) -> in
     """J: how many of its 4 * tiles sample maxima per query a shard sends. theta is the j-th
     largest of all shards' maxima with j <= J (J from the catalog-wide k', the same on every
     rank), and the j-th largest of the union of each shard's J largest is that same value.
-    0 = no shared threshold (the sample would decide nothing). driver.hip shard_layout."""
+    0 = no shared threshold (the sample would decide nothing). sharded.hip shard_layout."""
     m_total = 256 * tiles * world
     J = spec_rank(kp_glob * m_total / max(n_global, 1))
     if J > world * 4 * tiles // 2:
@@ -348,7 +348,7 @@ def theta_from_samples(g: torch.Tensor, qb, kprime: int, tiles: int, n_global: i
     maxima per query each shard sent (J of sample_send_width; the gathered rows of a packed
     send carry one extra -inf column, G = J + 1): the j-th largest of the union is exact for
     j <= sent, and for any j <= RG / 2 when every shard sent all of its 4 * tiles maxima
-    (driver.hip makes the same decision)."""
+    (sharded.hip makes the same decision)."""
     R, B, G = g.shape
     m_total = 256 * tiles * R
     RG = R * 4 * tiles

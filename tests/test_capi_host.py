@@ -245,7 +245,7 @@ def test_shared_threshold_plan():
 def test_shared_sample_tiles_c_and_python_agree():
     """the sample's fill to one round of the persistent grid stays within the caps
     (<= 64 tiles per shard, world * 4 * tiles <= 2048 maxima per query, ebt_pool_kth's limit) in
-    C (driver.hip sh_tiles, through ebt_shard_sample_tiles) and Python
+    C (sharded.hip sh_tiles, through ebt_shard_sample_tiles) and Python
     (distributed.shared_sample_tiles) alike: the two paths take the same decision for every
     config, e.g. B_pad = 512 on 8 ranks with 196K-300K-row shards (a round there is 128 tiles)."""
     from robot_ebert_amd import _lib

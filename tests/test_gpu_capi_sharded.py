@@ -69,6 +69,13 @@ def lib():
         VP, VP, VP, VP, SZ, VP, VP, VP, ctypes.POINTER(ShardedPending), VP, VP]
     h.ebt_cosine_topk_sharded_finish.argtypes = [ctypes.POINTER(ShardedPending)]
     h.ebt_cosine_topk_sharded_wait.argtypes = [ctypes.POINTER(ShardedPending)]
+    h.ebt_shard_sample_tiles.argtypes = [I64, I32, I64]
+    h.ebt_shard_sample_tiles.restype = I64
+    h.ebt_timer_create.restype = VP
+    h.ebt_timer_destroy.argtypes = [VP]
+    h.ebt_timer_destroy.restype = None
+    h.ebt_timer_query.argtypes = [VP, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                  ctypes.POINTER(I64)]
     return h
 
 
@@ -89,12 +96,15 @@ def shard_cuts(n, world):
 
 
 REDUCE = ctypes.CFUNCTYPE(ctypes.c_int, VP, VP, SZ, VP)
+STAGE_RESCORE = 4   # EBT_STAGE_RESCORE
 
 
 def run_ranks(lib, hip, full, world, k, q=None, liked=None, excl=None, fail_rank=-1,
-              allreduce=False, opt=None):
+              allreduce=False, opt=None, timer=False):
     """ebt_cosine_topk_sharded on `world` thread ranks; returns per-rank (rc, message, s, r).
-    allreduce: the comm also offers all_reduce_f64 (a barrier exchange summing in rank order)."""
+    allreduce: the comm also offers all_reduce_f64 (a barrier exchange summing in rank order).
+    timer: every rank passes an ebt_timer of its own and queries its rescore stage afterwards;
+    a third value is returned, per rank (query rc, total ms, launches)."""
     dev = full.device
     n = full.shape[0]
     cuts = shard_cuts(n, world)
@@ -106,6 +116,7 @@ def run_ranks(lib, hip, full, world, k, q=None, liked=None, excl=None, fail_rank
         cat.row_offset = cuts[r]
         cats.append((cat, state))
     out = [None] * world
+    timed = [None] * world
 
     def body(rank):
         def gather(ctx, send, recv, nbytes, stream):
@@ -156,11 +167,18 @@ def run_ranks(lib, hip, full, world, k, q=None, liked=None, excl=None, fail_rank
         rr = torch.full((B, k), -2, dtype=torch.int64, device=dev)
         lo, lr = liked if liked is not None else (None, None)
         eo, er = excl if excl is not None else (None, None)
+        tm = lib.ebt_timer_create() if timer else None
+        assert tm or not timer
         rc = lib.ebt_cosine_topk_sharded(
             ctypes.byref(cat), ctypes.byref(comm), P(q), CODE[q.dtype] if q is not None else 0, B,
             q.stride(0) if q is not None else 0, P(lo), P(lr), k, P(eo), P(er), optp, P(ws), need,
-            P(s), P(rr), None, torch.cuda.current_stream(dev).cuda_stream)
+            P(s), P(rr), tm, torch.cuda.current_stream(dev).cuda_stream)
         msg = lib.ebt_last_error().decode() if rc else ""
+        if timer:
+            ms, launches = ctypes.c_double(-1.0), I64(-1)
+            qrc = lib.ebt_timer_query(tm, STAGE_RESCORE, ctypes.byref(ms), ctypes.byref(launches))
+            timed[rank] = (qrc, ms.value, launches.value)
+            lib.ebt_timer_destroy(tm)
         out[rank] = (rc, msg, s.cpu().numpy(), rr.cpu().numpy())
     ts = [threading.Thread(target=body, args=(r,)) for r in range(world)]
     for t in ts:
@@ -170,6 +188,8 @@ def run_ranks(lib, hip, full, world, k, q=None, liked=None, excl=None, fail_rank
     assert all(o is not None for o in out), "a rank did not finish"
     if allreduce:
         return out, shared["calls"], shared["reduces"]
+    if timer:
+        return out, shared["calls"], timed
     return out, shared["calls"]
 
 
@@ -208,6 +228,28 @@ def test_sharded_capi_shared_threshold_exclusions(cuda_device, lib, hip):
                                  [excl[i] for i in sample])
     np.testing.assert_array_equal(r1[sample], r_ref)
     np.testing.assert_allclose(s1[sample], s_ref, rtol=0, atol=1e-12)
+
+
+@pytest.mark.parametrize("n, B, shared_threshold", [(49152, 160, True), (4096, 8, False)])
+def test_sharded_capi_with_timer(cuda_device, lib, hip, n, B, shared_threshold):
+    """A caller's ebt_timer through the sharded entry, in process and at small size: 2 ranks, f32
+    catalog, dense queries, d = 64, top-10. n = 49152 with B = 160 (B_pad 256) is the smallest
+    shape at which the shared-threshold branch is taken; n = 4096 with B = 8 takes the other.
+    Rows and scores are bitwise those of the same call without a timer and of the single-GPU
+    entry, and every rank's rescore stage reports at least one launch and a finite total >= 0."""
+    d, k, world = 64, 10, 2
+    B_pad = 128 if B <= 128 else (B + 255) // 256 * 256
+    assert (lib.ebt_shard_sample_tiles(n, world, B_pad) > 0) == shared_threshold
+    full = torch.from_numpy(gaussian(231, n, d, "f32").astype(np.float32)).to(cuda_device)
+    q = torch.from_numpy(gaussian(232, B, d, "f32").astype(np.float32)).to(cuda_device)
+    plain, _ = run_ranks(lib, hip, full, world, k, q=q)
+    res, _, timed = run_ranks(lib, hip, full, world, k, q=q, timer=True)
+    check_equal_single(lib, full, res, k, q=q)
+    for (rc0, msg0, s0, r0), (rc, msg, s, r), (qrc, ms, launches) in zip(plain, res, timed):
+        assert rc0 == 0 and rc == 0, (msg0, msg)
+        np.testing.assert_array_equal(r, r0)
+        assert s.tobytes() == s0.tobytes()
+        assert qrc == 0 and launches >= 1 and np.isfinite(ms) and ms >= 0.0, (qrc, ms, launches)
 
 
 def test_sharded_capi_local_retries_repack(cuda_device, lib, hip):
