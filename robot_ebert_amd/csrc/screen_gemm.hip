@@ -363,6 +363,23 @@ __device__ __forceinline__ void qp2_mma(f32x4_t (&acc)[4][2], const u16x8_t (&a)
         acc[i][j] = mfma16<BF16>(a[i][ks], b[j][ks], acc[i][j]);
 }
 
+// A tile's first phase on an accumulator: the first k-step takes the inline constant 0 as C (the
+// same bits as adding to a cleared register), so the accumulators are never cleared.
+template <bool BF16>
+__device__ __forceinline__ void qp2_mma_z(f32x4_t (&acc)[4][2], const u16x8_t (&a)[4][2],
+                                          const u16x8_t (&b)[2][2]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      acc[i][j] = mfma16<BF16>(a[i][0], b[j][0], f32x4_t{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      acc[i][j] = mfma16<BF16>(a[i][1], b[j][1], acc[i][j]);
+}
+
 // Epilogue modes of the quadrant-phase kernel: EPI_STORE (score rows), EPI_FILTER (the fused
 // screen's hit slots), EPI_POOL (the speculative screen's sample: per query and 64-row subgroup
 // only the MAX score, S[q][4 ct + 2 ah + wa] -- 64x less output than the scores).
@@ -579,7 +596,9 @@ __device__ unsigned long long* g_walk;
 __device__ unsigned long long* g_stamps;
 #endif
 
-template <bool BF16, int EPI, bool ODD>
+// ZC (filter mode, at least 4 K-tiles per tile; chosen by launch_gemm): the tile's first K-tile
+// pair runs ahead of the loop with zero-C MFMAs (qp2_mma_z) in place of clearing the accumulators.
+template <bool BF16, int EPI, bool ODD, bool ZC = false>
 __global__ __launch_bounds__(QP_THREADS, 2) void screen_gemm_qp2_kernel(QpArgs args) {
   (void)args;  // read through qp_args()
   constexpr bool FILTER = EPI == EPI_FILTER;
@@ -787,12 +806,12 @@ __global__ __launch_bounds__(QP_THREADS, 2) void screen_gemm_qp2_kernel(QpArgs a
   // and local index of K-tile t+1 (its A1 is issued in Q1), (RC2, RQ2, K2): of K-tile t+2.
   // The LDS-DMA pieces live in the same basic block as the MFMAs and are spread between them by
   // the sched_group_barrier patterns (masks: 0x008 MFMA, 0x100 DS read, 0x020 VMEM read).
-#define QP2_KTILE(P, s0, s1, RC1, RQ1, K1, RC2, RQ2, K2, READ_NEXT)                             \
+#define QP2_KTILE_(MMA, P, s0, s1, RC1, RQ1, K1, RC2, RQ2, K2, READ_NEXT)                       \
   {                                                                                             \
     /* Q1 (A0, B0): read B1(t) */                                                               \
     qp_barrier();                                                                               \
     issue_h(RC1, RQ1, K1, P_A1, 1 - (P));                                                       \
-    qp2_mma<BF16>(acc0, fa0, s0);                                                               \
+    MMA<BF16>(acc0, fa0, s0);                                                                   \
     read_b(s1, (P), P_B1);                                                                      \
     __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                          \
     __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                          \
@@ -810,7 +829,7 @@ __global__ __launch_bounds__(QP_THREADS, 2) void screen_gemm_qp2_kernel(QpArgs a
     /* Q2 (A0, B1): read A1(t) */                                                               \
     qp_barrier();                                                                               \
     issue_h(RC2, RQ2, K2, P_A0, (P));                                                           \
-    qp2_mma<BF16>(acc1, fa0, s1);                                                               \
+    MMA<BF16>(acc1, fa0, s1);                                                                   \
     read_a(fa1, (P), P_A1);                                                                     \
     __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                          \
     __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                          \
@@ -827,7 +846,7 @@ __global__ __launch_bounds__(QP_THREADS, 2) void screen_gemm_qp2_kernel(QpArgs a
     /* Q3 (A1, B1): no reads */                                                                 \
     qp_barrier();                                                                               \
     issue_h(RC2, RQ2, K2, P_B0, (P));                                                           \
-    qp2_mma<BF16>(acc2, fa1, s1);                                                               \
+    MMA<BF16>(acc2, fa1, s1);                                                                   \
     __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                          \
     __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                                          \
     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                                          \
@@ -837,7 +856,7 @@ __global__ __launch_bounds__(QP_THREADS, 2) void screen_gemm_qp2_kernel(QpArgs a
     /* Q4 (A1, B0): read A0(t+1), B0(t+1) */                                                    \
     qp_barrier();                                                                               \
     issue_h(RC2, RQ2, K2, P_B1, (P));                                                           \
-    qp2_mma<BF16>(acc3, fa1, s0);                                                               \
+    MMA<BF16>(acc3, fa1, s0);                                                                   \
     if (READ_NEXT) {                                                                            \
       read_a(fa0, 1 - (P), P_A0);                                                               \
       read_b(s1, 1 - (P), P_B0);                                                                \
@@ -865,6 +884,8 @@ __global__ __launch_bounds__(QP_THREADS, 2) void screen_gemm_qp2_kernel(QpArgs a
     wait_vm<8>(); /* B1(t+1) for Q1(t+1) */                                                     \
   }
 
+#define QP2_KTILE(...) QP2_KTILE_(qp2_mma, __VA_ARGS__)
+
 #ifdef EBT_WALK_STAMP
   int walk_t = 0;
 #endif
@@ -887,10 +908,20 @@ __global__ __launch_bounds__(QP_THREADS, 2) void screen_gemm_qp2_kernel(QpArgs a
       const QpTile T = tile_at(L);
       const __amdgpu_buffer_rsrc_t rc = rsrc_c(T), rq = rsrc_q(T);
       // K-tiles 0 .. kt-3 of the tile (pairs), then the boundary pair that stages the next tile
-      zero_acc();
-      for (int t = 0; t < kt - 2; t += 2) {
-        QP2_KTILE(0, fbx, fby, rc, rq, t + 1, rc, rq, t + 2, true);
-        QP2_KTILE(1, fby, fbx, rc, rq, t + 2, rc, rq, t + 3, true);
+      if constexpr (ZC) {
+        // kt >= 4: the first pair issues the halves the loop's first iteration would
+        QP2_KTILE_(qp2_mma_z, 0, fbx, fby, rc, rq, 1, rc, rq, 2, true);
+        QP2_KTILE(1, fby, fbx, rc, rq, 2, rc, rq, 3, true);
+        for (int t = 2; t < kt - 2; t += 2) {
+          QP2_KTILE(0, fbx, fby, rc, rq, t + 1, rc, rq, t + 2, true);
+          QP2_KTILE(1, fby, fbx, rc, rq, t + 2, rc, rq, t + 3, true);
+        }
+      } else {
+        zero_acc();
+        for (int t = 0; t < kt - 2; t += 2) {
+          QP2_KTILE(0, fbx, fby, rc, rq, t + 1, rc, rq, t + 2, true);
+          QP2_KTILE(1, fby, fbx, rc, rq, t + 2, rc, rq, t + 3, true);
+        }
       }
       const QpTile N = tile_at(last ? L : L + n_x);
       const __amdgpu_buffer_rsrc_t nc = rsrc_c(N), nq = rsrc_q(N);
@@ -898,6 +929,17 @@ __global__ __launch_bounds__(QP_THREADS, 2) void screen_gemm_qp2_kernel(QpArgs a
       QP2_KTILE(1, fby, fbx, nc, nq, 0, nc, nq, 1, false);
     }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (EPI == EPI_POOL) {
+      // pool mode: the accumulators as opaque values here (no instruction). Without it the
+      // allocator renames one quadrant's accumulator through the boundary pair and spills 16
+      // bytes per lane once per tile (a scratch store and reload inside the operand stream).
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj)
+          asm volatile("" : "+v"(acc0[i][jj]), "+v"(acc1[i][jj]), "+v"(acc2[i][jj]),
+                            "+v"(acc3[i][jj]));
+    }
     EPI_STAMP(0);
     EPI_COUNT(5);
     // the epilogue's lane geometry is recomputed from an opaque copy of the lane id, so that
@@ -1318,6 +1360,7 @@ __global__ __launch_bounds__(QP_THREADS, 2) void screen_gemm_qp2_kernel(QpArgs a
     issue_params(tile_at(L));
   }
 #undef QP2_KTILE
+#undef QP2_KTILE_
   // the last tile restaged its own first K-tiles: drain before the LDS is released
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #ifdef EBT_EPI_STAMP
@@ -1425,10 +1468,20 @@ static int launch_gemm(const void* qimg, int64_t B_pad, const void* cimg, int64_
 #endif
     const int ktiles = d_pad / 64;
     dim3 grid((unsigned)G), block(QP_THREADS);
-    auto k = (ktiles & 1) ? (img_dtype == EBT_BF16 ? screen_gemm_qp2_kernel<true, EPI, true>
-                                                   : screen_gemm_qp2_kernel<false, EPI, true>)
-                          : (img_dtype == EBT_BF16 ? screen_gemm_qp2_kernel<true, EPI, false>
-                                                   : screen_gemm_qp2_kernel<false, EPI, false>);
+    // the zero-C instantiation (filter mode only: the store epilogue spills with it) needs a
+    // K-tile pair ahead of the boundary pair: at least 4 K-tiles after the odd pad
+    constexpr bool ZC_EPI = EPI == EPI_FILTER;
+    const bool zc = ZC_EPI && ktiles + (ktiles & 1) >= 4;
+    const bool bf = img_dtype == EBT_BF16;
+    auto k = (ktiles & 1) ? (bf ? screen_gemm_qp2_kernel<true, EPI, true>
+                                : screen_gemm_qp2_kernel<false, EPI, true>)
+                          : (bf ? screen_gemm_qp2_kernel<true, EPI, false>
+                                : screen_gemm_qp2_kernel<false, EPI, false>);
+    if (zc)
+      k = (ktiles & 1) ? (bf ? screen_gemm_qp2_kernel<true, EPI, true, ZC_EPI>
+                             : screen_gemm_qp2_kernel<false, EPI, true, ZC_EPI>)
+                       : (bf ? screen_gemm_qp2_kernel<true, EPI, false, ZC_EPI>
+                             : screen_gemm_qp2_kernel<false, EPI, false, ZC_EPI>);
     set_max_lds((const void*)k, QP_LDS_TOTAL);
     QpArgs a{};
     a.Q = Q;

@@ -91,9 +91,11 @@ def trivepi(src):
 
 
 def nozero(src):
-    # diagnostic (wrong results): the accumulators are not cleared between tiles
-    return _sub(src, "      zero_acc();\n      for (int t = 0; t < kt - 2; t += 2) {",
-                "      for (int t = 0; t < kt - 2; t += 2) {", 1)
+    # diagnostic (wrong results): the accumulators are not cleared between tiles. The clear is
+    # left only in the ZC = false instantiations (store, pool, and the filter below 4 K-tiles per
+    # tile); the zero-C filter instantiation never clears, so there this variant equals `base`
+    return _sub(src, "        zero_acc();\n        for (int t = 0; t < kt - 2; t += 2) {",
+                "        for (int t = 0; t < kt - 2; t += 2) {", 1)
 
 
 def nocoltest(src):
@@ -128,7 +130,8 @@ def build(name):
     os.makedirs(work, exist_ok=True)
     if not os.path.exists(os.path.join(base, "include")):
         os.symlink(os.path.join(ROOT, "include"), os.path.join(base, "include"))
-    shutil.copy(os.path.join(CSRC, "common.h"), work)
+    for h in ("common.h", "internal.h", "driver.h"):
+        shutil.copy(os.path.join(CSRC, h), work)
     with open(os.path.join(work, "screen_gemm.hip"), "w") as f:
         f.write(src)
     obj = os.path.join(work, "screen_gemm.o")
@@ -136,12 +139,16 @@ def build(name):
              "-Wno-unused-function", "-I" + os.path.join(ROOT, "include")]
     subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-c", os.path.join(work, "screen_gemm.hip"),
                                                       "-o", obj], check=True)
+    # the product's other objects (make -C robot_ebert_amd/csrc first), in the Makefile's order
     others = [os.path.join(CSRC, "build", f) for f in
-              ("api.o", "driver.o", "select_topk.o", "prep.o", "rescore.o", "als.o")]
+              ("api.o", "driver.o", "select_topk.o", "prep.o", "catalog_update.o", "rescore.o",
+               "als.o", "large_k.o", "csr_sort.o", "rccl_comm.o", "allow_mask.o", "subcatalog.o",
+               "sharded.o")]
     os.makedirs(OUT, exist_ok=True)
     lib = os.path.join(OUT, f"libebert_{name}.so")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-shared", "--offload-arch=gfx950", "-o", lib, obj]
-                   + others + ["-Wl,-rpath,/opt/rocm/lib"], check=True)
+    subprocess.run(["/opt/rocm/bin/hipcc", "-shared", "--offload-arch=gfx950", "-o", lib]
+                   + others[:2] + [obj] + others[2:] + ["-ldl", "-Wl,-rpath,/opt/rocm/lib"],
+                   check=True)
     print("built", lib)
 
 
