@@ -110,7 +110,92 @@ def nocoltest(src):
 """ + src[b:]
 
 
-VARIANTS = {"nozero": nozero, "nocoltest": nocoltest, "trivepi": trivepi, "noepi": noepi, "noepi_nofin": noepi_nofin, "l2only": l2only, "nobar": nobar, "nowait": nowait, "grp2": grp(2), "grp8": grp(8), "grp16": grp(16),"base": lambda s: s, "nosleep": nosleep, "prio_static": prio_static,
+# Arithmetic-only faults (wrong results) for tests/test_gpu_screen_exact_ints.py: each drops or
+# alters one arithmetic instruction and touches no address, descriptor, barrier, wait count or
+# LDS offset (profiles/r13/gemm_exact/README.md: which test notices which).
+
+def _quadrant3(src, plain, body):
+    # quadrant Q3 (acc2) of a K-tile whose MFMA blocks are MMA calls MMA_q3f instead: the plain
+    # block for the names in `plain`, and what `body` defines for the one it alters
+    src = _sub(src, "MMA<BF16>(acc2, fa1, s1);", "MMA##_q3f<BF16>(acc2, fa1, s1);", 1)
+    fwd = "".join(f"""template <bool BF16>
+__device__ __forceinline__ void {n}_q3f(f32x4_t (&acc)[4][2], const u16x8_t (&a)[4][2],
+                                        const u16x8_t (&b)[2][2]) {{
+  {n}<BF16>(acc, a, b);
+}}
+""" for n in plain)
+    return _sub(src, "// Epilogue modes of the quadrant-phase kernel:", fwd + body +
+                "// Epilogue modes of the quadrant-phase kernel:", 1)
+
+
+def skip_mfma(src):
+    # the boundary pair's first K-tile: Q3 skips the MFMA (i = 2, j = 1) of its second k-step
+    src = _sub(src, "      QP2_KTILE(0, fbx, fby, rc, rq, kt - 1, nc, nq, 0, true);",
+               "      QP2_KTILE_(qp2_mma_b, 0, fbx, fby, rc, rq, kt - 1, nc, nq, 0, true);", 1)
+    return _quadrant3(src, ["qp2_mma", "qp2_mma_z"], """template <bool BF16>
+__device__ __forceinline__ void qp2_mma_b(f32x4_t (&acc)[4][2], const u16x8_t (&a)[4][2],
+                                          const u16x8_t (&b)[2][2]) {
+  qp2_mma<BF16>(acc, a, b);
+}
+template <bool BF16>
+__device__ __forceinline__ void qp2_mma_b_q3f(f32x4_t (&acc)[4][2], const u16x8_t (&a)[4][2],
+                                              const u16x8_t (&b)[2][2]) {
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        if (!(ks == 1 && i == 2 && j == 1)) acc[i][j] = mfma16<BF16>(a[i][ks], b[j][ks], acc[i][j]);
+}
+""")
+
+
+def stale_zc(src):
+    # the ZC instantiations: Q3's first zero-C MFMA accumulates onto the previous tile's value
+    return _quadrant3(src, ["qp2_mma"], """template <bool BF16>
+__device__ __forceinline__ void qp2_mma_z_q3f(f32x4_t (&acc)[4][2], const u16x8_t (&a)[4][2],
+                                              const u16x8_t (&b)[2][2]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      acc[i][j] = mfma16<BF16>(a[i][0], b[j][0],
+                               i == 0 && j == 0 ? acc[i][j] : f32x4_t{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      acc[i][j] = mfma16<BF16>(a[i][1], b[j][1], acc[i][j]);
+}
+""")
+
+
+def pool_noshfl32(src):
+    # the pool epilogue's maximum over the lanes 32 apart is left out
+    return _sub(src, "      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));\n", "", 1)
+
+
+def hit_gt(src):
+    # the persistent kernel's filter keeps > thr instead of >= thr (both staging layouts)
+    return _sub(src, "hb |= (v[k] >= th && (full ||", "hb |= (v[k] > th && (full ||", 2)
+
+
+def small_hit_gt(src):
+    # the same in the 128 x 128 kernel's append path (its all-miss test keeps >=)
+    return _sub(src, "    if (i < n_rows && v[r] >= th) {", "    if (i < n_rows && v[r] > th) {", 1)
+
+
+def small_cs0(src):
+    # the 128 x 128 kernel's epilogue scales all four rows of an accumulator by the first row's
+    return _sub(src, "row_scales4(cscale, i0, n_rows), lcnt, grp);",
+                "[&] { const float4 c4 = row_scales4(cscale, i0, n_rows);\n"
+                "      return make_float4(c4.x, c4.x, c4.x, c4.x); }(), lcnt, grp);", 1)
+
+
+VARIANTS = {"skip_mfma": skip_mfma, "stale_zc": stale_zc, "pool_noshfl32": pool_noshfl32,
+            "hit_gt": hit_gt, "small_hit_gt": small_hit_gt, "small_cs0": small_cs0,
+            "nozero": nozero, "nocoltest": nocoltest, "trivepi": trivepi, "noepi": noepi, "noepi_nofin": noepi_nofin, "l2only": l2only, "nobar": nobar, "nowait": nowait, "grp2": grp(2), "grp8": grp(8), "grp16": grp(16),"base": lambda s: s, "nosleep": nosleep, "prio_static": prio_static,
             "prio_static_sleep": prio_static_sleep}
 
 
