@@ -83,7 +83,10 @@ extern "C" {
  *        at most 1 KiB).
  * 0.7.0: materialised sub-catalogs: ebt_allow_count, ebt_allow_rows_bytes, ebt_allow_rows,
  *        ebt_catalog_gather_rows, ebt_sub_exclusions_bytes, ebt_sub_exclusions,
- *        ebt_sub_rows_to_global (additive; no existing entry, struct or kernel changes). */
+ *        ebt_sub_rows_to_global (additive; no existing entry, struct or kernel changes).
+ * 0.8.0: per-row weights on liked-row queries: ebt_query_liked_wsum, ebt_cosine_topk_weighted /
+ *        _weighted_submit, ebt_cosine_topk_sharded_weighted / _sharded_weighted_submit
+ *        (additive; liked_w == NULL launches the kernels of 0.7.0; no workspace size changes). */
 int ebt_version(void);
 
 /* Message for the last non-zero return on this thread ("" if none). */
@@ -839,6 +842,76 @@ int ebt_cosine_topk_sharded(const ebt_catalog* cat, const ebt_comm* comm, const 
                             const int64_t* excl_rows, const ebt_options* opt, void* workspace,
                             size_t ws_bytes, double* out_scores, int64_t* out_rows, void* timer,
                             void* stream);
+
+/* ---- weighted and negative feedback (0.8.0): per-row weights on liked-row queries -----------
+ * The reference turns a rating into a 0/1 vote (lib.py:47-52: rating >= LIKED_MOVIE_SCORE is a
+ * liked row, the query is the plain mean of the liked rows) and uses everything below the
+ * threshold only as an exclusion. These entries generalise that mean: with weights w_l (device
+ * float64, one per entry of liked_rows, in the same order) on the liked rows r_l of query b,
+ * l in [liked_off[b], liked_off[b+1]),
+ *   score_b(j) = ( sum_l w_l cos(x_{r_l}, x_j) ) / W_b,       W_b = sum_l |w_l|
+ *   q64[b]     = ( sum_l w_l (x_{r_l} / gnorm64[r_l]) ) * (1 / W_b).
+ * A weight may be negative ("unlike this": the row pushes away), and liked_rows may repeat a
+ * row (each entry is its own term). |q64[b]| <= 1 as for the mean (the triangle inequality over
+ * unit vectors, divided by W_b), so the screen, its eps, the certificate, the rescore and every
+ * retry run unchanged on q64: only the query prep sees the weights.
+ * The arithmetic is fixed, so that results can be compared bitwise: the per-element term is the
+ * rounded product w * (x / g) (no fused multiply-add), added in CSR order -- the element and
+ * the 16-byte-chunk kernels give the same bits, and weights of 1.0 give ebt_query_liked_sum's;
+ * W_b is the sequential float64 sum of |w_l| in CSR order; the scale is 1.0 / W_b, applied as
+ * ebt_scale_rows_f64 applies 1 / L. The host check and the device (EBT_FLAG_LIKED_CHECKED)
+ * compute the identical W_b. Hence: all weights 1.0 = the unweighted call; weights times a power
+ * of two = the same result; a 0.0 weight = that entry removed.
+ *
+ * ebt_query_liked_wsum: ebt_query_liked_sum with the weights (still a SUM: the caller scales).
+ * ebt_cosine_topk_weighted / _weighted_submit: the arguments of ebt_cosine_topk_allowed /
+ * _allowed_submit (allow may be NULL) plus liked_w. liked_w == NULL is exactly that entry: the
+ * same kernels, the same bits. liked_w with dense q is EBT_EINVAL. A batch is finished with
+ * ebt_cosine_topk_allowed_finish (ebt_pending holds nothing of the liked CSR). Found before any
+ * scoring work, EBT_EINVAL with a message naming the query: a NaN or infinite weight, W_b == 0
+ * (a query with no liked row gives sklearn's message first, as always). With
+ * EBT_FLAG_LIKED_CHECKED the caller vouches for the weights as well (all finite, W_b > 0):
+ * nothing is read back, the submit stays asynchronous, 1 / W_b is computed on the device.
+ * The weights are the caller's device memory, valid for as long as liked_rows must be; the
+ * per-query scale uses the liked path's existing scratch, so workspace sizes do not change
+ * (ebt_workspace_bytes / ebt_sharded_workspace_bytes).
+ * ebt_cosine_topk_sharded_weighted / _sharded_weighted_submit: every rank passes the same
+ * GLOBAL CSR and the same weights; each shard sums its own rows weighted, the partial sums are
+ * exchanged exactly as the unweighted ones (the caller's all-reduce, or the gather added in rank
+ * order), then scaled by 1 / W_b, which every rank computes from the full list. _finish and
+ * _wait are the unweighted entries'. */
+int ebt_query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld,
+                         const double* gnorm64_cat, int64_t B, const int64_t* liked_off,
+                         const int64_t* liked_rows, const double* liked_w, double* q64,
+                         void* stream);
+int ebt_cosine_topk_weighted(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                             int64_t ldq, const int64_t* liked_off, const int64_t* liked_rows,
+                             int32_t k, const int64_t* excl_off, const int64_t* excl_rows,
+                             const ebt_options* opt, void* workspace, size_t ws_bytes,
+                             double* out_scores, int64_t* out_rows, void* timer, void* stream,
+                             const ebt_allow* allow, const double* liked_w);
+int ebt_cosine_topk_weighted_submit(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                                    int64_t ldq, const int64_t* liked_off,
+                                    const int64_t* liked_rows, int32_t k, const int64_t* excl_off,
+                                    const int64_t* excl_rows, const ebt_options* opt,
+                                    void* workspace, size_t ws_bytes, double* out_scores,
+                                    int64_t* out_rows, int32_t* cert_host, ebt_pending* pending,
+                                    void* timer, void* stream, const ebt_allow* allow,
+                                    const double* liked_w);
+int ebt_cosine_topk_sharded_weighted(const ebt_catalog* cat, const ebt_comm* comm, const void* q,
+                                     int q_dtype, int64_t B, int64_t ldq,
+                                     const int64_t* liked_off, const int64_t* liked_rows,
+                                     int32_t k, const int64_t* excl_off,
+                                     const int64_t* excl_rows, const ebt_options* opt,
+                                     void* workspace, size_t ws_bytes, double* out_scores,
+                                     int64_t* out_rows, void* timer, void* stream,
+                                     const double* liked_w);
+int ebt_cosine_topk_sharded_weighted_submit(
+    const ebt_catalog* cat, const ebt_comm* comm, const void* q, int q_dtype, int64_t B,
+    int64_t ldq, const int64_t* liked_off, const int64_t* liked_rows, int32_t k,
+    const int64_t* excl_off, const int64_t* excl_rows, const ebt_options* opt, void* workspace,
+    size_t ws_bytes, double* out_scores, int64_t* out_rows, int32_t* host,
+    ebt_sharded_pending* pending, void* timer, void* stream, const double* liked_w);
 
 /* ---- two-phase top-k over a row-sharded catalog (robot_ebert_amd/distributed.py) ---------
  * Phase 1, every rank: ebt_cosine_screen = ebt_cosine_topk_prepared without the rescore: the shard's k'

@@ -15,6 +15,10 @@ mask_ids))`` returns the top k of (allowed rows minus excluded rows). A sparse m
 materialised (ABI 0.7.0): ``masks.materialize(mask)`` copies its allowed rows into a dense
 sub-catalog (``SubCatalog``) and the queries of that mask are then scored over those rows alone,
 with the same rows and bitwise the same scores.
+
+Liked rows can carry weights (ABI 0.8.0): ``score_topk(..., liked=, liked_weights=)`` scores by
+sum_l w_l cos(x_l, x) / sum_l |w_l| (negative weights push away), through every path the
+unweighted call has; ``lib.get_user_recs(..., weighting=)`` maps a user's ratings to weights.
 """
 from ._lib import EbertError, Timer, load  # noqa: F401
 from .catalog import Catalog  # noqa: F401

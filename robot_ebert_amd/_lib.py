@@ -121,6 +121,18 @@ _SIGNATURES = {
                                         _POPT, _VP, _SZ, _VP, _VP, _VP, _PPEND, _VP, _VP,
                                         _PALLOW], _INT),
     "ebt_cosine_topk_allowed_finish": ([_PPEND, _PALLOW], _INT),
+    "ebt_query_liked_wsum": ([_VP, _INT, _I32, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP], _INT),
+    "ebt_cosine_topk_weighted": ([_PCAT, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP, _POPT,
+                                  _VP, _SZ, _VP, _VP, _VP, _VP, _PALLOW, _VP], _INT),
+    "ebt_cosine_topk_weighted_submit": ([_PCAT, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP,
+                                         _POPT, _VP, _SZ, _VP, _VP, _VP, _PPEND, _VP, _VP,
+                                         _PALLOW, _VP], _INT),
+    "ebt_cosine_topk_sharded_weighted": ([_PCAT, _PCOMM, _VP, _INT, _I64, _I64, _VP, _VP, _I32,
+                                          _VP, _VP, _POPT, _VP, _SZ, _VP, _VP, _VP, _VP, _VP],
+                                         _INT),
+    "ebt_cosine_topk_sharded_weighted_submit": ([_PCAT, _PCOMM, _VP, _INT, _I64, _I64, _VP, _VP,
+                                                 _I32, _VP, _VP, _POPT, _VP, _SZ, _VP, _VP, _VP,
+                                                 _PSPEND, _VP, _VP, _VP], _INT),
     "ebt_allow_count": ([_VP, _I64, _I64, _VP, _VP], _INT),
     "ebt_allow_rows_bytes": ([_I64], _SZ),
     "ebt_allow_rows": ([_VP, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _SZ, _VP], _INT),

@@ -35,6 +35,10 @@ concurrently, SURVEY §8b "Threading") only the dispatcher does.
   list, so the requests of a materialised mask (``AllowMasks.materialize``) are scored over its
   sub-catalog; every edit leaves those copies stale until the caller materialises again.
 
+* Weighted requests: ``submit(..., weights=)`` gives every liked row a float weight (negative:
+  "unlike this"); the request is checked on its own and shares batches with unweighted ones
+  (``score_topk_submit(..., liked_weights=)``, 1.0 for their rows).
+
 Per-request semantics are those of ``lib.get_user_recs``: a request without liked rows fails
 with sklearn's ValueError (alone -- the rest of its batch is unaffected), results are
 (scores float64, global rows int64) ordered (score desc, row asc).
@@ -143,11 +147,16 @@ class RecBatcher:
 
     # ---- request side (any thread) -----------------------------------------------------------
     def submit(self, liked_rows: Sequence[int], exclude_rows: Sequence[int], k: int,
-               allow=None) -> Future:
+               allow=None, weights: Optional[Sequence[float]] = None) -> Future:
         """Queue one user's request; the Future resolves to (scores [k'], rows [k']) numpy arrays
         (k' <= k: fewer when the catalog has fewer candidates) or raises the request's error.
         allow: None, or the index or name of one of ``allow_masks``: only the rows that mask
-        allows are candidates. A bad index or name fails this request alone."""
+        allows are candidates. A bad index or name fails this request alone.
+        weights: None, or one float per liked row (ebert.h 0.8.0: the score is the weighted mean
+        cosine, sum_l w_l cos / sum_l |w_l|; negative weights push away). Checked here: a wrong
+        length, a non-finite value or sum |w| == 0 fails this request alone. Weighted and
+        unweighted requests share batches: the batch then goes out with ``liked_weights=`` and
+        1.0 for every row of its unweighted members, which gives them the unweighted answer."""
         fut: Future = Future()
         mask = -1
         if allow is not None:
@@ -184,13 +193,33 @@ class RecBatcher:
             bad = next(r for r in liked if r < lo or r >= hi)
             fut.set_exception(ValueError(f"liked row {bad} is not in the catalog rows [{lo}, {hi})"))
             return fut
+        w = None
+        if weights is not None:
+            try:
+                w = [float(x) for x in weights]
+            except (TypeError, ValueError, OverflowError) as e:
+                fut.set_exception(ValueError(f"malformed weights: {e}"))
+                return fut
+            if len(w) != len(liked):
+                fut.set_exception(ValueError(f"{len(w)} weights for {len(liked)} liked rows"))
+                return fut
+            if not all(np.isfinite(x) for x in w):
+                fut.set_exception(ValueError("liked weights must be finite"))
+                return fut
+            W = 0.0
+            for x in w:
+                W += abs(x)
+            if not (W > 0.0 and np.isfinite(W)):
+                fut.set_exception(ValueError(f"liked weights sum to |w| = {W}: a finite sum > 0 "
+                                             "is required"))
+                return fut
         # rated rows outside the catalog cannot match a candidate: dropped, as lib.py:48's
         # catalog.index.difference(rated) ignores unknown ids. k past the catalog returns every
         # candidate (the Future holds at most n rows): the same answer from a k the library can size
         if n > 0:
             rated = [r for r in rated if lo <= r < hi]
             k = min(k, int(getattr(self.catalog, "n_global", n)))
-        item = (liked, sorted(set(rated)), k, fut, mask)
+        item = (liked, sorted(set(rated)), k, fut, mask, w)
         with self._lock:   # a request is either queued before close()'s sentinel or refused
             if self._closed:
                 fut.set_exception(RuntimeError("batcher is closed"))
@@ -339,6 +368,12 @@ class RecBatcher:
         kw = {}
         if any(r[4] >= 0 for r in reqs):
             kw["allow"] = (self.allow_masks, [r[4] for r in reqs])
+        # likewise the weights: only a batch with a weighted request carries the keyword, and
+        # its unweighted members weigh every liked row 1.0 (bitwise the unweighted answer)
+        weighted = any(r[5] is not None for r in reqs)
+        if weighted:
+            kw["liked_weights"] = [r[5] if r[5] is not None else [1.0] * len(r[0])
+                                   for r in reqs]
         if not self._pipelined:
             try:
                 scores, rows = self._score(self.catalog, k_max, liked=liked, exclude=excl, **kw)
@@ -360,9 +395,13 @@ class RecBatcher:
             if self.stager is not None and nbytes >= self.stage_min_bytes:
                 # the batch's CSRs through the copy stream (pinned staging), then its kernels;
                 # an event right after them for its results' D2H
-                from .search import csr_from_lists
+                from .search import csr_from_lists, csr_from_weighted_lists
                 dev = self.catalog.device
-                liked = csr_from_lists(liked, dev, self.stager)
+                if weighted:
+                    liked, kw["liked_weights"] = csr_from_weighted_lists(
+                        liked, kw["liked_weights"], dev, self.stager)
+                else:
+                    liked = csr_from_lists(liked, dev, self.stager)
                 excl = csr_from_lists(excl, dev, self.stager)
                 p = submit(self.catalog, k_max, liked=liked, exclude=excl, **kw)
                 ev = self.stager.record()

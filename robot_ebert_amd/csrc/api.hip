@@ -638,7 +638,7 @@ using namespace ebt;
 
 extern "C" {
 
-int ebt_version(void) { return 700; }  // 0.7.0: materialised sub-catalogs (ebert.h)
+int ebt_version(void) { return 800; }  // 0.8.0: per-row weights on liked-row queries (ebert.h)
 
 const char* ebt_last_error(void) { return g_err; }
 
@@ -664,6 +664,14 @@ int ebt_query_liked_sum(const void* cat, int dtype, int32_t d, int64_t ld,
                         const int64_t* liked_rows, double* q64, void* stream) {
   return query_liked_sum(cat, dtype, d, ld, gnorm64_cat, B, liked_off, liked_rows, q64,
                          (hipStream_t)stream);
+}
+
+int ebt_query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld,
+                         const double* gnorm64_cat, int64_t B, const int64_t* liked_off,
+                         const int64_t* liked_rows, const double* liked_w, double* q64,
+                         void* stream) {
+  return query_liked_wsum(cat, dtype, d, ld, gnorm64_cat, B, liked_off, liked_rows, liked_w, q64,
+                          (hipStream_t)stream);
 }
 
 int ebt_query_prep(const void* q, int dtype, int64_t B, int64_t B_pad, int32_t d, int64_t ldq,

@@ -45,9 +45,11 @@ bool driver_layout(const ebt_catalog& c, int64_t B, int32_t k, const ebt_options
                    DriverLayout* L);
 int prep_dense(const ebt_catalog& c, const void* q, int q_dtype, int64_t B, int64_t ldq,
                const PrepLayout& P, char* base, hipStream_t st);
-// the host checks of a liked batch (rows in [row_lo, row_hi)); (*scale)[b] = 1 / L_b
+// the host checks of a liked batch (rows in [row_lo, row_hi)); (*scale)[b] = 1 / L_b, or with
+// weights w (device, parallel to rows; checked finite, sum_l |w_l| > 0) 1 / sum_l |w_l|
 int liked_scales(const int64_t* off, const int64_t* rows, int64_t B, int32_t d, int64_t row_lo,
-                 int64_t row_hi, std::vector<double>* scale, hipStream_t st);
+                 int64_t row_hi, std::vector<double>* scale, hipStream_t st,
+                 const double* w = nullptr);
 
 // ---- the tail of a submit ----------------------------------------------------------------------
 // *ev = an event of the pool, recorded on st (returned to the pool on failure)

@@ -189,8 +189,10 @@ int prep_dense(const ebt_catalog& c, const void* q, int q_dtype, int64_t B, int6
 
 // The host checks of a liked batch: every query likes at least one row (sklearn's message) and
 // every liked row is in [row_lo, row_hi); (*scale)[b] = 1 / L_b. One stream sync.
+// With weights w (device float64, parallel to rows): every weight finite and W_b = sum_l |w_l|
+// (sequential, CSR order: scale_by_abs_weight_sum_kernel's sum) > 0; (*scale)[b] = 1 / W_b.
 int liked_scales(const int64_t* off, const int64_t* rows, int64_t B, int32_t d, int64_t row_lo,
-                 int64_t row_hi, std::vector<double>* scale, hipStream_t st) {
+                 int64_t row_hi, std::vector<double>* scale, hipStream_t st, const double* w) {
   std::vector<int64_t> h_off(B + 1);
   int rc = hip_check(hipMemcpyAsync(h_off.data(), off, (B + 1) * 8, hipMemcpyDeviceToHost, st),
                      "hipMemcpyAsync");
@@ -218,6 +220,29 @@ int liked_scales(const int64_t* off, const int64_t* rows, int64_t B, int32_t d, 
                   (long long)row_lo, (long long)row_hi);
         return EBT_EINVAL;
       }
+  }
+  if (w) {
+    std::vector<double> h_w(nnz);
+    rc = hip_check(hipMemcpy(h_w.data(), w + h_off[0], nnz * 8, hipMemcpyDeviceToHost),
+                   "hipMemcpy");
+    if (rc) return rc;
+    for (int64_t b = 0; b < B; ++b) {
+      double W = 0.0;
+      for (int64_t l = h_off[b] - h_off[0]; l < h_off[b + 1] - h_off[0]; ++l) {
+        if (!std::isfinite(h_w[l])) {
+          set_error("liked weight %lld of query %lld is not finite", (long long)(l + h_off[0]),
+                    (long long)b);
+          return EBT_EINVAL;
+        }
+        W += std::fabs(h_w[l]);
+      }
+      if (!(W > 0.0) || !std::isfinite(W)) {
+        set_error("the liked weights of query %lld sum to |w| = %g (a finite sum > 0 is "
+                  "required)", (long long)b, W);
+        return EBT_EINVAL;
+      }
+      (*scale)[b] = 1.0 / W;
+    }
   }
   return EBT_OK;
 }
@@ -330,16 +355,17 @@ __global__ void scale_by_count_kernel(double* __restrict__ q64, int64_t total, i
 }
 
 // liked path: validated on the host (counts >= 1 with sklearn's message, rows in the catalog),
-// unless the caller did (EBT_FLAG_LIKED_CHECKED): then nothing is read back
-int prep_liked(const ebt_catalog& c, const int64_t* off, const int64_t* rows, int64_t B,
-               const PrepLayout& P, char* base, char* scratch, size_t scratch_bytes,
+// unless the caller did (EBT_FLAG_LIKED_CHECKED): then nothing is read back. w != NULL: the
+// weighted sum and 1 / W_b in place of the sum and 1 / L_b (w == NULL launches what it always did)
+int prep_liked(const ebt_catalog& c, const int64_t* off, const int64_t* rows, const double* w,
+               int64_t B, const PrepLayout& P, char* base, char* scratch, size_t scratch_bytes,
                hipStream_t st, bool checked) {
   double* q64 = (double*)(base + P.q64);
   double* d_scale = (double*)scratch;
   int rc = EBT_OK;
   if (!checked) {
     std::vector<double> scale;
-    rc = liked_scales(off, rows, B, c.d, c.row_offset, c.row_offset + c.n, &scale, st);
+    rc = liked_scales(off, rows, B, c.d, c.row_offset, c.row_offset + c.n, &scale, st, w);
     if (rc) return rc;
     if (scratch_bytes < (size_t)B * 8) {
       set_error("ebt_cosine_topk: workspace too small for the liked-query scales");
@@ -348,10 +374,14 @@ int prep_liked(const ebt_catalog& c, const int64_t* off, const int64_t* rows, in
     rc = hip_check(hipMemcpy(d_scale, scale.data(), B * 8, hipMemcpyHostToDevice), "hipMemcpy");
     if (rc) return rc;
   }
-  rc = query_liked_sum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, q64, st,
-                       c.row_offset, 0);
+  rc = w ? query_liked_wsum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, w, q64, st,
+                            c.row_offset, 0)
+         : query_liked_sum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, q64, st,
+                           c.row_offset, 0);
   if (rc) return rc;
-  if (checked) {
+  if (checked && w) {
+    rc = scale_by_abs_weight_sum(q64, B, c.d, off, w, st);
+  } else if (checked) {
     int64_t blocks = ceil_div(B * c.d, 256);
     blocks = blocks > 8192 ? 8192 : blocks;
     hipLaunchKernelGGL(scale_by_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, q64,
@@ -397,15 +427,22 @@ size_t ebt_workspace_bytes(const ebt_catalog* cat, int64_t B, int32_t k, const e
 }
 
 // ebt_cosine_topk_submit (allow = NULL) and ebt_cosine_topk_allowed_submit: with per-query allow
-// masks the batch runs unfused (EBT_FLAG_NO_FUSE set here, and kept in the pending batch)
-int ebt_cosine_topk_allowed_submit(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
-                                   int64_t ldq, const int64_t* liked_off,
-                                   const int64_t* liked_rows, int32_t k, const int64_t* excl_off,
-                                   const int64_t* excl_rows, const ebt_options* opt,
-                                   void* workspace, size_t ws_bytes, double* out_scores,
-                                   int64_t* out_rows, int32_t* cert_host, ebt_pending* p,
-                                   void* timer, void* stream, const ebt_allow* allow) {
+// masks the batch runs unfused (EBT_FLAG_NO_FUSE set here, and kept in the pending batch).
+// ebt_cosine_topk_weighted_submit is the same entry with per-row weights on the liked rows
+// (liked_w == NULL: exactly the unweighted batch); only the query prep sees them.
+int ebt_cosine_topk_weighted_submit(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                                    int64_t ldq, const int64_t* liked_off,
+                                    const int64_t* liked_rows, int32_t k, const int64_t* excl_off,
+                                    const int64_t* excl_rows, const ebt_options* opt,
+                                    void* workspace, size_t ws_bytes, double* out_scores,
+                                    int64_t* out_rows, int32_t* cert_host, ebt_pending* p,
+                                    void* timer, void* stream, const ebt_allow* allow,
+                                    const double* liked_w) {
   hipStream_t st = (hipStream_t)stream;
+  if (liked_w && q) {
+    set_error("ebt_cosine_topk_weighted: liked_w weighs liked rows; dense queries (q) take none");
+    return EBT_EINVAL;
+  }
   if (!valid_catalog(cat) || !p || !workspace || !out_scores || !out_rows || !cert_host ||
       B < 1 || k < 1 || ((q == nullptr) == (liked_off == nullptr)) ||
       (liked_off && !liked_rows) || ((excl_off == nullptr) != (excl_rows == nullptr)) ||
@@ -444,7 +481,7 @@ int ebt_cosine_topk_allowed_submit(const ebt_catalog* cat, const void* q, int q_
   char* ws = (char*)workspace;
   char* prep = ws + L.off_prep;
   int rc = q ? prep_dense(*cat, q, q_dtype, B, ldq, L.prep, prep, st)
-             : prep_liked(*cat, liked_off, liked_rows, B, L.prep, prep,
+             : prep_liked(*cat, liked_off, liked_rows, liked_w, B, L.prep, prep,
                           ws + (L.large ? L.off_big : L.off_pass),
                           L.large ? L.big_bytes : L.pass_bytes, st,
                           (o.flags & EBT_FLAG_LIKED_CHECKED) != 0);
@@ -487,6 +524,19 @@ int ebt_cosine_topk_allowed_submit(const ebt_catalog* cat, const void* q, int q_
   fill_pending(p, cat, o, B, k, L, excl_off, excl_rows, ws, ws_bytes, out_scores, out_rows,
                cert_host, ev, timer, stream);
   return EBT_OK;
+}
+
+int ebt_cosine_topk_allowed_submit(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                                   int64_t ldq, const int64_t* liked_off,
+                                   const int64_t* liked_rows, int32_t k, const int64_t* excl_off,
+                                   const int64_t* excl_rows, const ebt_options* opt,
+                                   void* workspace, size_t ws_bytes, double* out_scores,
+                                   int64_t* out_rows, int32_t* cert_host, ebt_pending* p,
+                                   void* timer, void* stream, const ebt_allow* allow) {
+  return ebt_cosine_topk_weighted_submit(cat, q, q_dtype, B, ldq, liked_off, liked_rows, k,
+                                         excl_off, excl_rows, opt, workspace, ws_bytes,
+                                         out_scores, out_rows, cert_host, p, timer, stream, allow,
+                                         nullptr);
 }
 
 int ebt_cosine_topk_submit(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
@@ -693,22 +743,33 @@ int ebt_cosine_topk_allowed_finish(ebt_pending* p, const ebt_allow* allow) {
 
 int ebt_cosine_topk_finish(ebt_pending* p) { return ebt_cosine_topk_allowed_finish(p, nullptr); }
 
+int ebt_cosine_topk_weighted(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
+                             int64_t ldq, const int64_t* liked_off, const int64_t* liked_rows,
+                             int32_t k, const int64_t* excl_off, const int64_t* excl_rows,
+                             const ebt_options* opt, void* workspace, size_t ws_bytes,
+                             double* out_scores, int64_t* out_rows, void* timer, void* stream,
+                             const ebt_allow* allow, const double* liked_w) {
+  std::vector<int32_t> cert((size_t)(B > 0 ? B : 0) + 1);
+  ebt_pending p{};
+  int rc = ebt_cosine_topk_weighted_submit(cat, q, q_dtype, B, ldq, liked_off, liked_rows, k,
+                                           excl_off, excl_rows, opt, workspace, ws_bytes,
+                                           out_scores, out_rows, cert.data(), &p, timer, stream,
+                                           allow, liked_w);
+  if (rc) return rc;
+  rc = ebt_cosine_topk_allowed_finish(&p, allow);
+  if (!rc) rc = hip_check(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
+  return rc;
+}
+
 int ebt_cosine_topk_allowed(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B,
                             int64_t ldq, const int64_t* liked_off, const int64_t* liked_rows,
                             int32_t k, const int64_t* excl_off, const int64_t* excl_rows,
                             const ebt_options* opt, void* workspace, size_t ws_bytes,
                             double* out_scores, int64_t* out_rows, void* timer, void* stream,
                             const ebt_allow* allow) {
-  std::vector<int32_t> cert((size_t)(B > 0 ? B : 0) + 1);
-  ebt_pending p{};
-  int rc = ebt_cosine_topk_allowed_submit(cat, q, q_dtype, B, ldq, liked_off, liked_rows, k,
-                                          excl_off, excl_rows, opt, workspace, ws_bytes,
-                                          out_scores, out_rows, cert.data(), &p, timer, stream,
-                                          allow);
-  if (rc) return rc;
-  rc = ebt_cosine_topk_allowed_finish(&p, allow);
-  if (!rc) rc = hip_check(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
-  return rc;
+  return ebt_cosine_topk_weighted(cat, q, q_dtype, B, ldq, liked_off, liked_rows, k, excl_off,
+                                  excl_rows, opt, workspace, ws_bytes, out_scores, out_rows,
+                                  timer, stream, allow, nullptr);
 }
 
 int ebt_cosine_topk(const ebt_catalog* cat, const void* q, int q_dtype, int64_t B, int64_t ldq,

@@ -107,6 +107,12 @@ int query_dense(const void* q, int dtype, int64_t B, int32_t d, int64_t ldq, dou
 int query_liked_sum(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm,
                     int64_t B, const int64_t* off, const int64_t* rows, double* q64,
                     hipStream_t st, int64_t row_offset = 0, int64_t n_local = 0);
+// the weighted sum sum_l w_l x_l / g_l (wts parallel to rows), and q64[b] *= 1 / sum_l |w_l|
+int query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm,
+                     int64_t B, const int64_t* off, const int64_t* rows, const double* wts,
+                     double* q64, hipStream_t st, int64_t row_offset = 0, int64_t n_local = 0);
+int scale_by_abs_weight_sum(double* q64, int64_t B, int32_t d, const int64_t* off,
+                            const double* wts, hipStream_t st);
 int scale_rows_f64(double* q64, int64_t B, int32_t d, const double* scale, hipStream_t st);
 int query_image(const double* q64, int64_t B, int64_t B_pad, int32_t d, int img_dtype,
                 const void* q_native, int64_t ldq, int native_q, float u_cat, void* qimg,

@@ -9,6 +9,9 @@
 //                      a multiple of 64 columns.
 //  * query_dense / query_liked_sum / scale_rows -- q64 = normalize(q), or the liked-row mean of
 //                      lib.py:51-52 folded into ONE query vector per user (sum here, 1/L later).
+//  * query_liked_wsum / scale_by_abs_weight_sum -- the same fold with a float64 weight per liked
+//                      row (ABI 0.8.0: lib.py:47-52's 0/1 vote generalised): sum_l w_l x_l/|x_l|,
+//                      then 1 / sum_l |w_l|.
 //  * query_image    -- the query's MFMA operand, its epilogue scale and the certification bound.
 //  * mask_excluded  -- rated movies are not candidates (lib.py:48,55).
 #include "common.h"
@@ -419,6 +422,168 @@ int query_liked_sum(const void* cat, int dtype, int32_t d, int64_t ld, const dou
     default: hipLaunchKernelGGL(query_liked_kernel<EBT_F64>, grid, block, 0, st, cat, d, ld, gnorm, off, rows, row_offset, n_local, q64); break;
   }
   return launch_check("query_liked_kernel");
+}
+
+// ------------------------------------------------------- weighted liked rows (ABI 0.8.0) ----
+// q64[b] = sum_l w_l (x_{r_l} / gnorm[r_l]) in CSR order: the two kernels above with one multiply
+// per row (their instantiations are not touched). The term is the ROUNDED product w * (x / g),
+// then added: no fused multiply-add, so that the element form, the chunk form and a float64 host
+// loop give the same bits (and a weight of 1.0 gives the unweighted kernels' bits).
+__device__ __forceinline__ double weighted_term(double w, double xg) {
+#pragma clang fp contract(off)
+  const double t = w * xg;
+  return t;
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void query_liked_w_kernel(
+    const void* __restrict__ cat, int d, int64_t ld, const double* __restrict__ gnorm,
+    const int64_t* __restrict__ off, const int64_t* __restrict__ rows,
+    const double* __restrict__ wts, int64_t row_offset, int64_t n_local,
+    double* __restrict__ q64) {
+  const int64_t b = blockIdx.x;
+  const int64_t l0 = off[b], l1 = off[b + 1];
+  for (int j = threadIdx.x; j < d; j += blockDim.x) {
+    double acc = 0.0;
+    for (int64_t l = l0; l < l1; ++l) {
+      const int64_t r = rows[l] - row_offset;
+      if (n_local > 0 && (r < 0 || r >= n_local)) continue;
+      acc += weighted_term(wts[l], load_as_f64<DT>(cat, r * ld + j) / gnorm[r]);
+    }
+    q64[b * d + j] = acc;
+  }
+}
+
+// the chunk form: the weights staged in LDS beside the rows and norms
+template <int DT>
+__global__ __launch_bounds__(256) void query_liked_w_vec_kernel(
+    const void* __restrict__ cat, int d, int64_t ld, const double* __restrict__ gnorm,
+    const int64_t* __restrict__ off, const int64_t* __restrict__ rows,
+    const double* __restrict__ wts, int64_t row_offset, int64_t n_local,
+    double* __restrict__ q64) {
+  constexpr int ES = DT == EBT_F64 ? 8 : (DT == EBT_F32 ? 4 : 2);
+  constexpr int PER = 16 / ES;   // elements per 16-byte chunk
+  __shared__ int64_t srow[QL_STAGE];
+  __shared__ double sg[QL_STAGE];
+  __shared__ double sw[QL_STAGE];
+  const int64_t b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int64_t l0 = off[b], l1 = off[b + 1];
+  const int nch = d / PER;
+  constexpr int QL_CPT = 2;   // chunks per thread (d <= 256 * PER * QL_CPT)
+  double acc[QL_CPT][PER];
+#pragma unroll
+  for (int i = 0; i < QL_CPT; ++i)
+#pragma unroll
+    for (int e = 0; e < PER; ++e) acc[i][e] = 0.0;
+  for (int64_t s0 = l0; s0 < l1; s0 += QL_STAGE) {
+    const int ns = l1 - s0 < QL_STAGE ? (int)(l1 - s0) : QL_STAGE;
+    __syncthreads();
+    if (tid < ns) {
+      const int64_t r = rows[s0 + tid] - row_offset;
+      const bool skip = n_local > 0 && (r < 0 || r >= n_local);   // another shard's row
+      srow[tid] = skip ? -1 : r;
+      sg[tid] = skip ? 1.0 : gnorm[r];
+      sw[tid] = wts[s0 + tid];
+    }
+    __syncthreads();
+    for (int u0 = 0; u0 < ns; u0 += QL_UL) {
+#pragma unroll
+      for (int i = 0; i < QL_CPT; ++i) {
+        const int c = tid + 256 * i;
+        if (c >= nch) break;
+        uint4 raw[QL_UL];
+#pragma unroll
+        for (int u = 0; u < QL_UL; ++u) {   // loads first (a skipped / past-the-end row reads row 0)
+          const int64_t r = u0 + u < ns ? srow[u0 + u] : -1;
+          raw[u] = *(const uint4*)((const char*)cat + ((r >= 0 ? r : 0) * ld + (int64_t)c * PER) * ES);
+        }
+#pragma unroll
+        for (int u = 0; u < QL_UL; ++u) {
+          if (u0 + u >= ns || srow[u0 + u] < 0) continue;
+          const double g = sg[u0 + u];
+          const double w = sw[u0 + u];
+#pragma unroll
+          for (int e = 0; e < PER; ++e) {
+            double x;
+            if constexpr (DT == EBT_F32) x = (double)((const float*)&raw[u])[e];
+            else if constexpr (DT == EBT_F64) x = ((const double*)&raw[u])[e];
+            else if constexpr (DT == EBT_BF16) x = bf16_bits_to_f64(((const uint16_t*)&raw[u])[e]);
+            else x = f16_bits_to_f64(((const uint16_t*)&raw[u])[e]);
+            acc[i][e] += weighted_term(w, x / g);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < QL_CPT; ++i) {
+    const int c = tid + 256 * i;
+    if (c >= nch) break;
+#pragma unroll
+    for (int e = 0; e < PER; ++e) q64[b * d + (int64_t)c * PER + e] = acc[i][e];
+  }
+}
+
+int query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm,
+                     int64_t B, const int64_t* off, const int64_t* rows, const double* wts,
+                     double* q64, hipStream_t st, int64_t row_offset, int64_t n_local) {
+  if (!cat || !gnorm || !off || !rows || !wts || !q64 || B < 0 || d <= 0 || ld < d || dtype < 0 ||
+      dtype > 3) {
+    set_error("ebt_query_liked_wsum: bad arguments");
+    return EBT_EINVAL;
+  }
+  if (B == 0) return EBT_OK;
+  dim3 grid((unsigned)B), block(256);
+  const int es = dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2);
+  const int per = 16 / es;
+  const bool vec = ((uintptr_t)cat & 15) == 0 && (ld * es) % 16 == 0 && d % per == 0 &&
+                   d <= 256 * per * 2;
+#define EBT_QLW(DT)                                                                            \
+  if (vec)                                                                                     \
+    hipLaunchKernelGGL(query_liked_w_vec_kernel<DT>, grid, block, 0, st, cat, d, ld, gnorm,    \
+                       off, rows, wts, row_offset, n_local, q64);                              \
+  else                                                                                         \
+    hipLaunchKernelGGL(query_liked_w_kernel<DT>, grid, block, 0, st, cat, d, ld, gnorm, off,   \
+                       rows, wts, row_offset, n_local, q64)
+  switch (dtype) {
+    case EBT_F32: EBT_QLW(EBT_F32); break;
+    case EBT_BF16: EBT_QLW(EBT_BF16); break;
+    case EBT_F16: EBT_QLW(EBT_F16); break;
+    default: EBT_QLW(EBT_F64); break;
+  }
+#undef EBT_QLW
+  return launch_check(vec ? "query_liked_w_vec_kernel" : "query_liked_w_kernel");
+}
+
+// q64[b] *= 1 / W_b, W_b = the sequential float64 sum of |w_l| over the query's CSR segment (the
+// value the host check computes, then scale_rows_kernel's product): the weighted twin of the
+// driver's scale by 1 / L for a CSR the caller has checked. One block per query; thread 0 sums.
+__global__ __launch_bounds__(256) void scale_by_abs_weight_sum_kernel(
+    double* __restrict__ q64, int d, const int64_t* __restrict__ off,
+    const double* __restrict__ wts) {
+  __shared__ double s_scale;
+  const int64_t b = blockIdx.x;
+  if (threadIdx.x == 0) {
+    double W = 0.0;
+    for (int64_t l = off[b]; l < off[b + 1]; ++l) W += fabs(wts[l]);
+    s_scale = 1.0 / W;
+  }
+  __syncthreads();
+  const double s = s_scale;
+  for (int j = threadIdx.x; j < d; j += blockDim.x) q64[b * d + j] *= s;
+}
+
+int scale_by_abs_weight_sum(double* q64, int64_t B, int32_t d, const int64_t* off,
+                            const double* wts, hipStream_t st) {
+  if (!q64 || !off || !wts || B < 0 || d <= 0) {
+    set_error("scale_by_abs_weight_sum: bad arguments");
+    return EBT_EINVAL;
+  }
+  if (B == 0) return EBT_OK;
+  hipLaunchKernelGGL(scale_by_abs_weight_sum_kernel, dim3((unsigned)B), dim3(256), 0, st, q64, d,
+                     off, wts);
+  return launch_check("scale_by_abs_weight_sum_kernel");
 }
 
 __global__ void scale_rows_kernel(double* q64, int64_t total, int d, const double* scale) {

@@ -179,18 +179,22 @@ int sh_gather(const ebt_comm& cm, const void* send, void* recv, size_t bytes, vo
 }
 
 // liked rows of a row-sharded catalog: GLOBAL rows, each shard sums its own, the partial sums
-// are all-gathered and added in rank order, then / L_b (lib.py:51-52)
+// are all-gathered and added in rank order, then / L_b (lib.py:51-52). With weights w (the
+// same global list on every rank): each shard's weighted sum of its own rows, then / W_b, which
+// every rank computes from the full list
 int prep_liked_sharded(const ebt_catalog& c, const ebt_comm& cm, const int64_t* off,
-                       const int64_t* rows, int64_t B, const PrepLayout& P, char* base,
-                       double* d_scale, double* qrecv, void* timer, hipStream_t st) {
+                       const int64_t* rows, const double* w, int64_t B, const PrepLayout& P,
+                       char* base, double* d_scale, double* qrecv, void* timer, hipStream_t st) {
   std::vector<double> scale;
-  int rc = liked_scales(off, rows, B, c.d, 0, cm.n_global, &scale, st);
+  int rc = liked_scales(off, rows, B, c.d, 0, cm.n_global, &scale, st, w);
   if (rc) return rc;
   rc = hip_check(hipMemcpy(d_scale, scale.data(), B * 8, hipMemcpyHostToDevice), "hipMemcpy");
   if (rc) return rc;
   double* q64 = (double*)(base + P.q64);
-  rc = query_liked_sum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, q64, st,
-                       c.row_offset, c.n);
+  rc = w ? query_liked_wsum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, w, q64, st,
+                            c.row_offset, c.n)
+         : query_liked_sum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, q64, st,
+                           c.row_offset, c.n);
   if (rc) return rc;
   if (cm.all_reduce_f64) {  // the caller's all-reduce (RCCL: about 2 / R of the gather's bytes)
     if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_COLLECTIVE, st);
@@ -244,14 +248,19 @@ size_t ebt_sharded_workspace_bytes(const ebt_catalog* cat, const ebt_comm* comm,
   return S.bytes;
 }
 
-int ebt_cosine_topk_sharded_submit(const ebt_catalog* cat, const ebt_comm* comm, const void* q,
-                                   int q_dtype, int64_t B, int64_t ldq,
-                                   const int64_t* liked_off, const int64_t* liked_rows,
-                                   int32_t k, const int64_t* excl_off, const int64_t* excl_rows,
-                                   const ebt_options* opt, void* workspace, size_t ws_bytes,
-                                   double* out_scores, int64_t* out_rows, int32_t* host,
-                                   ebt_sharded_pending* pending, void* timer, void* stream) {
+// ebt_cosine_topk_sharded_submit is this entry with liked_w == NULL
+int ebt_cosine_topk_sharded_weighted_submit(
+    const ebt_catalog* cat, const ebt_comm* comm, const void* q, int q_dtype, int64_t B,
+    int64_t ldq, const int64_t* liked_off, const int64_t* liked_rows, int32_t k,
+    const int64_t* excl_off, const int64_t* excl_rows, const ebt_options* opt, void* workspace,
+    size_t ws_bytes, double* out_scores, int64_t* out_rows, int32_t* host,
+    ebt_sharded_pending* pending, void* timer, void* stream, const double* liked_w) {
   hipStream_t st = (hipStream_t)stream;
+  if (liked_w && q) {
+    set_error("ebt_cosine_topk_sharded_weighted: liked_w weighs liked rows; dense queries (q) "
+              "take none");
+    return EBT_EINVAL;
+  }
   if (!valid_catalog(cat) || !comm || !workspace || !out_scores || !out_rows || !host ||
       !pending || B < 1 || k < 1 || ((q == nullptr) == (liked_off == nullptr)) ||
       (liked_off && !liked_rows) || ((excl_off == nullptr) != (excl_rows == nullptr)) ||
@@ -288,7 +297,7 @@ int ebt_cosine_topk_sharded_submit(const ebt_catalog* cat, const ebt_comm* comm,
   // 1. the queries (lib.py:51-52)
   if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_PREP, st);
   rc = q ? prep_dense(c, q, q_dtype, B, ldq, L.prep, prep, st)
-         : prep_liked_sharded(c, cm, liked_off, liked_rows, B, L.prep, prep,
+         : prep_liked_sharded(c, cm, liked_off, liked_rows, liked_w, B, L.prep, prep,
                               (double*)(ws + S.off_scale), (double*)(ws + S.off_qrecv), timer, st);
   if (timer) (void)ebt_timer_end(timer, EBT_STAGE_PREP, st);
   if (rc) return rc;
@@ -425,6 +434,19 @@ int ebt_cosine_topk_sharded_submit(const ebt_catalog* cat, const ebt_comm* comm,
   return EBT_OK;
 }
 
+int ebt_cosine_topk_sharded_submit(const ebt_catalog* cat, const ebt_comm* comm, const void* q,
+                                   int q_dtype, int64_t B, int64_t ldq,
+                                   const int64_t* liked_off, const int64_t* liked_rows,
+                                   int32_t k, const int64_t* excl_off, const int64_t* excl_rows,
+                                   const ebt_options* opt, void* workspace, size_t ws_bytes,
+                                   double* out_scores, int64_t* out_rows, int32_t* host,
+                                   ebt_sharded_pending* pending, void* timer, void* stream) {
+  return ebt_cosine_topk_sharded_weighted_submit(cat, comm, q, q_dtype, B, ldq, liked_off,
+                                                 liked_rows, k, excl_off, excl_rows, opt,
+                                                 workspace, ws_bytes, out_scores, out_rows, host,
+                                                 pending, timer, stream, nullptr);
+}
+
 int ebt_cosine_topk_sharded_finish(ebt_sharded_pending* p) {
   if (!p || p->stage != 1 || !p->local.cat) {
     set_error("ebt_cosine_topk_sharded_finish: not a submitted batch");
@@ -518,20 +540,34 @@ int64_t ebt_shard_sample_tiles(int64_t n_global, int32_t world, int64_t B_pad) {
   return sh_tiles(n_global, world, B_pad);
 }
 
+int ebt_cosine_topk_sharded_weighted(const ebt_catalog* cat, const ebt_comm* comm, const void* q,
+                                     int q_dtype, int64_t B, int64_t ldq,
+                                     const int64_t* liked_off, const int64_t* liked_rows,
+                                     int32_t k, const int64_t* excl_off,
+                                     const int64_t* excl_rows, const ebt_options* opt,
+                                     void* workspace, size_t ws_bytes, double* out_scores,
+                                     int64_t* out_rows, void* timer, void* stream,
+                                     const double* liked_w) {
+  std::vector<int32_t> host((size_t)(B > 0 ? B : 0) + 2);
+  ebt_sharded_pending p{};
+  int rc = ebt_cosine_topk_sharded_weighted_submit(cat, comm, q, q_dtype, B, ldq, liked_off,
+                                                   liked_rows, k, excl_off, excl_rows, opt,
+                                                   workspace, ws_bytes, out_scores, out_rows,
+                                                   host.data(), &p, timer, stream, liked_w);
+  if (!rc) rc = ebt_cosine_topk_sharded_finish(&p);
+  if (!rc) rc = ebt_cosine_topk_sharded_wait(&p);
+  return rc;
+}
+
 int ebt_cosine_topk_sharded(const ebt_catalog* cat, const ebt_comm* comm, const void* q,
                             int q_dtype, int64_t B, int64_t ldq, const int64_t* liked_off,
                             const int64_t* liked_rows, int32_t k, const int64_t* excl_off,
                             const int64_t* excl_rows, const ebt_options* opt, void* workspace,
                             size_t ws_bytes, double* out_scores, int64_t* out_rows, void* timer,
                             void* stream) {
-  std::vector<int32_t> host((size_t)(B > 0 ? B : 0) + 2);
-  ebt_sharded_pending p{};
-  int rc = ebt_cosine_topk_sharded_submit(cat, comm, q, q_dtype, B, ldq, liked_off, liked_rows,
+  return ebt_cosine_topk_sharded_weighted(cat, comm, q, q_dtype, B, ldq, liked_off, liked_rows,
                                           k, excl_off, excl_rows, opt, workspace, ws_bytes,
-                                          out_scores, out_rows, host.data(), &p, timer, stream);
-  if (!rc) rc = ebt_cosine_topk_sharded_finish(&p);
-  if (!rc) rc = ebt_cosine_topk_sharded_wait(&p);
-  return rc;
+                                          out_scores, out_rows, timer, stream, nullptr);
 }
 
 }  // extern "C"

@@ -33,8 +33,10 @@ import torch.distributed as dist
 from . import _lib
 from ._lib import EbertError, call, ptr, region, stream_of
 from .catalog import Catalog
-from .search import (KPRIME_MAX, MERGE_WAVE_KMAX, _round_up, csr_from_lists, csr_subset,
+from .search import (KPRIME_MAX, MERGE_WAVE_KMAX, _round_up, csr_from_lists,
+                     csr_from_weighted_lists, csr_subset,
                      default_kprime, merge_topk, pad_batch, pool_kth, prepare_queries, run_screen,
+                     _liked_with_weights,
                      sample_maxima, score_topk, score_topk_finish, score_topk_stages,
                      score_topk_submit, spec_rank, union_floor_gathered)
 
@@ -68,11 +70,30 @@ def gather_partials(scores: torch.Tensor, rows: torch.Tensor,
     return gs.view((world,) + tuple(scores.shape)), gr.view((world,) + tuple(rows.shape))
 
 
-def split_liked(liked: Sequence[Sequence[int]], begin: int, end: int):
-    """Per-user liked rows that fall into [begin, end), plus every user's total count."""
+def split_liked(liked: Sequence[Sequence[int]], begin: int, end: int, weights=None):
+    """Per-user liked rows that fall into [begin, end), plus every user's total count.
+    With weights (lists parallel to liked, ebert.h 0.8.0): (local rows, counts, local weights,
+    W) where W[b] = sum |w| over the user's WHOLE list, the sequential float64 sum every rank
+    computes alike; the weights are checked here (EbertError naming the query: a length that
+    differs from the liked list's, a non-finite weight, W == 0)."""
     local = [[r for r in l if begin <= r < end] for l in liked]
     counts = [len(l) for l in liked]
-    return local, counts
+    if weights is None:
+        return local, counts
+    import numpy as np
+    from .search import check_weights
+    if len(weights) != len(liked):
+        raise EbertError(f"{len(weights)} weight lists for {len(liked)} liked lists")
+    for b, (l, w) in enumerate(zip(liked, weights)):
+        if len(w) != len(l):
+            raise EbertError(f"query {b} has {len(w)} weights for {len(l)} liked rows")
+    local_w = [[float(x) for r, x in zip(l, w) if begin <= r < end]
+               for l, w in zip(liked, weights)]
+    off = np.zeros(len(liked) + 1, dtype=np.int64)
+    np.cumsum(counts, out=off[1:])
+    flat = np.array([float(x) for w in weights for x in w], dtype=np.float64)
+    wsum = check_weights(off, flat)
+    return local, counts, local_w, [float(x) for x in wsum]
 
 
 def split_update(rows: Sequence[int], vectors, catalog):
@@ -132,11 +153,20 @@ class TorchCollectives:
         return t
 
 
-def _liked_queries(catalog: Catalog, liked, coll):
-    local, counts = split_liked(liked, catalog.row_offset, catalog.row_offset + catalog.n)
+def _liked_queries(catalog: Catalog, liked, coll, weights=None):
+    """(local CSR, counts, the all-reduce hook) of a shard's liked queries; with weights also
+    (local weights on the device, W_b float64 [B]): prepare_queries' liked_weights / liked_wsum."""
     dev = catalog.device
-    return (csr_from_lists(local, dev), torch.tensor(counts, dtype=torch.int64, device=dev),
-            lambda q64: coll.all_reduce_sum(q64))
+    hook = lambda q64: coll.all_reduce_sum(q64)  # noqa: E731
+    if weights is None:
+        local, counts = split_liked(liked, catalog.row_offset, catalog.row_offset + catalog.n)
+        return (csr_from_lists(local, dev), torch.tensor(counts, dtype=torch.int64, device=dev),
+                hook)
+    local, counts, local_w, wsum = split_liked(liked, catalog.row_offset,
+                                               catalog.row_offset + catalog.n, weights)
+    csr, wt = csr_from_weighted_lists(local, local_w, dev, check=False)
+    return (csr, torch.tensor(counts, dtype=torch.int64, device=dev), hook, wt,
+            torch.tensor(wsum, dtype=torch.float64, device=dev))
 
 
 def _two_phase(catalog: Catalog, qb, k: int, kprime: int, exclude, chunk_rows, timer, flags,
@@ -173,18 +203,27 @@ def score_topk_sharded(catalog: Catalog, k: int, queries: Optional[torch.Tensor]
                        liked: Optional[Sequence[Sequence[int]]] = None,
                        exclude=None, group: Optional[dist.ProcessGroup] = None,
                        kprime: Optional[int] = None, chunk_rows: Optional[int] = None,
-                       timer=None, fuse: bool = True, collectives=None
+                       timer=None, fuse: bool = True, collectives=None, liked_weights=None
                        ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Global top-k over a row-sharded catalog, two-phase (see the module doc); every rank
     returns the same (scores f64 [B, k], GLOBAL rows i64 [B, k]). ``exclude``: per-query GLOBAL
-    rows (lists or device CSR). ``collectives`` replaces the torch.distributed calls (tests)."""
+    rows (lists or device CSR). ``collectives`` replaces the torch.distributed calls (tests).
+    ``liked_weights``: host lists parallel to ``liked`` (search.score_topk_submit): each shard
+    sums its own rows weighted, the all-reduce completes the sums, every rank divides by the
+    same W_b = sum |w| of the whole list."""
     coll = collectives if collectives is not None else TorchCollectives(group)
     dev = catalog.device
     if k < 1:
         raise EbertError("k must be >= 1")
     if exclude is not None and not isinstance(exclude, tuple):
         exclude = csr_from_lists(exclude, dev)
-    if liked is not None:
+    if liked_weights is not None and liked is None:
+        raise EbertError("liked_weights= weighs liked rows: pass liked=")
+    if liked is not None and liked_weights is not None:
+        liked_csr, counts, hook, wt, wsum = _liked_queries(catalog, liked, coll, liked_weights)
+        qb = prepare_queries(catalog, liked=liked_csr, liked_counts=counts, liked_sum_hook=hook,
+                             liked_weights=wt, liked_wsum=wsum)
+    elif liked is not None:
         liked_csr, counts, hook = _liked_queries(catalog, liked, coll)
         qb = prepare_queries(catalog, liked=liked_csr, liked_counts=counts, liked_sum_hook=hook)
     else:
@@ -402,7 +441,13 @@ def score_topk_sharded_local_stages(catalog: Catalog, k: int,
     batch's kernels. The last next() returns the pending batch."""
     coll = collectives if collectives is not None else TorchCollectives(group)
     liked_arg = counts_t = hook = None
-    if liked is not None:
+    weights = kw.pop("liked_weights", None)   # host lists parallel to liked (score_topk_sharded)
+    if weights is not None and liked is None:
+        raise EbertError("liked_weights= weighs liked rows: pass liked=")
+    if liked is not None and weights is not None:
+        liked_arg, counts_t, hook, kw["liked_weights"], kw["liked_wsum"] = _liked_queries(
+            catalog, liked, coll, weights)
+    elif liked is not None:
         liked_arg, counts_t, hook = _liked_queries(catalog, liked, coll)
     kw.setdefault("t_floor_hook", lambda v, e: _gathered_floor(coll, v, e, k, kw.get("timer")))
     B = int(queries.shape[0]) if queries is not None else len(liked)
@@ -704,26 +749,38 @@ class ShardedTopk:
                              + (f" (all-gather: {err!r})" if err is not None else ""))
 
     def submit(self, slot: int, queries: Optional[torch.Tensor] = None, liked=None,
-               exclude=None) -> None:
-        """Enqueue one batch into workspace `slot` (free: its previous batch waited)."""
+               exclude=None, liked_weights=None) -> None:
+        """Enqueue one batch into workspace `slot` (free: its previous batch waited).
+        liked_weights: as search.score_topk_submit's, over the GLOBAL liked lists every rank
+        passes (ebt_cosine_topk_sharded_weighted_submit)."""
         import ctypes
         dev = self.catalog.device
-        q_ptr, q_dt, ldq, lo, lr = None, 0, 0, None, None
+        q_ptr, q_dt, ldq, lo, lr, lw = None, 0, 0, None, None, None
+        if liked_weights is not None and (liked is None or queries is not None):
+            raise EbertError("liked_weights= weighs liked rows: pass liked= (and no queries=)")
         if queries is not None:
             require = queries.is_cuda and queries.dim() == 2 and queries.shape[0] == self.B
             if not require or queries.stride(1) != 1:
                 raise EbertError(f"queries must be a contiguous-row [B={self.B}, d] GPU tensor")
             q_ptr, q_dt, ldq = ptr(queries), _lib.DTYPE_CODE[queries.dtype], queries.stride(0)
+        elif liked_weights is not None:
+            (lo, lr), lw = _liked_with_weights(liked, liked_weights, dev)
         else:
             lo, lr = liked if isinstance(liked, tuple) else csr_from_lists(liked, dev)
         eo = er = None
         if exclude is not None:
             eo, er = exclude if isinstance(exclude, tuple) else csr_from_lists(exclude, dev)
-        self.keep[slot] = (queries, lo, lr, eo, er)
+        self.keep[slot] = (queries, lo, lr, eo, er, lw)
         ws, ws_bytes, s, r, host, pend = self._slot_args[slot]
-        rc = self._fn_submit(self._cat_ref, self._comm_ref, q_ptr, q_dt, self.B, ldq, ptr(lo),
-                             ptr(lr), self.k, ptr(eo), ptr(er), self._opt_ref, ws, ws_bytes, s, r,
-                             host, pend, self._timer_h, stream_of(dev))
+        if lw is not None:
+            rc = _lib.load().ebt_cosine_topk_sharded_weighted_submit(
+                self._cat_ref, self._comm_ref, q_ptr, q_dt, self.B, ldq, ptr(lo), ptr(lr), self.k,
+                ptr(eo), ptr(er), self._opt_ref, ws, ws_bytes, s, r, host, pend, self._timer_h,
+                stream_of(dev), ptr(lw))
+        else:
+            rc = self._fn_submit(self._cat_ref, self._comm_ref, q_ptr, q_dt, self.B, ldq, ptr(lo),
+                                 ptr(lr), self.k, ptr(eo), ptr(er), self._opt_ref, ws, ws_bytes,
+                                 s, r, host, pend, self._timer_h, stream_of(dev))
         if rc:
             self._check(rc, "submit")
 
@@ -739,9 +796,11 @@ class ShardedTopk:
         self.keep[slot] = None
         return self.out[slot]
 
-    def __call__(self, queries=None, liked=None, exclude=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def __call__(self, queries=None, liked=None, exclude=None,
+                 liked_weights=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """One batch, blocking (slot 0)."""
-        self.submit(0, queries=queries, liked=liked, exclude=exclude)
+        self.submit(0, queries=queries, liked=liked, exclude=exclude,
+                    liked_weights=liked_weights)
         self.finish(0)
         return self.wait(0)
 

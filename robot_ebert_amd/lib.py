@@ -119,6 +119,40 @@ def _user_request(user_id: str) -> Optional[Tuple[List[int], List[int]]]:
     return liked, rated
 
 
+def weight_by_rating(rating: float) -> float:
+    """A ``weighting``: a liked movie counts by its rating, r if r >= LIKED_MOVIE_SCORE else 0
+    (the reference's 0/1 vote of lib.py:47 with the rating kept; a 5.0 outweighs a 3.5)."""
+    return float(rating) if rating >= LIKED_MOVIE_SCORE else 0.0
+
+
+def weight_centered(rating: float) -> float:
+    """A ``weighting``: r - LIKED_MOVIE_SCORE, so that a disliked movie pushes away (a 0.5 weighs
+    -3.0, a 5.0 weighs +1.5, a 3.5 nothing)."""
+    return float(rating) - LIKED_MOVIE_SCORE
+
+
+def _user_request_weighted(user_id: str, weighting: Callable[[float], float]
+                           ) -> Optional[Tuple[List[int], List[int], List[float]]]:
+    """_user_request with ``weighting`` in place of lib.py:47's threshold: (rows, rated rows,
+    weights), one term per rating of a catalog movie whose weight is not zero, in row order of
+    the ratings; None when the user has no ratings; sklearn's ValueError when no term is left."""
+    cat = movies_collab_catalog
+    with engine.begin() as cnx:  # lib.py:36-40
+        statement = select(tables.ratings).where(tables.ratings.c.user_id == user_id)
+        user_ratings = cnx.execute(statement).all()
+        if not user_ratings:
+            return None
+    pos = cat.index_pos
+    kept = [(r.tmdb_id, r.rating) for r in user_ratings if r.tmdb_id in pos]  # lib.py:44
+    terms = [(t, float(weighting(rt))) for t, rt in kept]
+    terms = [(t, w) for t, w in terms if w != 0.0]
+    rated = cat.rows_of(list(dict.fromkeys(t for t, _ in kept)))              # lib.py:48
+    if not terms:  # sklearn check_pairwise_arrays on an empty X (lib.py:51)
+        raise ValueError(f"Found array with 0 sample(s) (shape=(0, {cat.d})) while a minimum of 1 "
+                         "is required by check_pairwise_arrays.")
+    return cat.rows_of([t for t, _ in terms]), rated, [w for _, w in terms]
+
+
 def _hydrate(s: np.ndarray, r: np.ndarray) -> List[Recommendation]:
     """lib.py:55-63 after the top-k: ids, sort_index, get_movies (ORDER BY id), zip, stable sort."""
     cat = movies_collab_catalog
@@ -138,7 +172,8 @@ def _allow_of(allow):
     return allow_masks, [allow_masks.index(allow)]
 
 
-def get_user_recs(user_id: str, k: int = 10, allow=None) -> List[Recommendation]:
+def get_user_recs(user_id: str, k: int = 10, allow=None,
+                  weighting: Optional[Callable[[float], float]] = None) -> List[Recommendation]:
     """GPU drop-in for lib.py:32-63 (same inputs, same outputs, same errors).
 
     Any k, as the reference's pandas `[:k]` (min(k, rows) > 4096 runs the full-sort path of
@@ -146,7 +181,22 @@ def get_user_recs(user_id: str, k: int = 10, allow=None) -> List[Recommendation]
 
     allow: None (the reference's function), or the index or name of one of the configured
     ``allow_masks``: the recommendations come from the rows that mask allows (unrated ones, as
-    always), min(k, rows) <= 4096."""
+    always), min(k, rows) <= 4096.
+
+    weighting: None (the reference's function: rating >= LIKED_MOVIE_SCORE is a 0/1 vote), or a
+    callable rating -> weight applied to every rated catalog movie (``weight_by_rating``,
+    ``weight_centered``): the score of a movie is sum_l w_l cos(x_l, x) / sum_l |w_l| over the
+    rated movies with a non-zero weight; when none is left, sklearn's empty-array ValueError.
+    Rated movies stay excluded either way."""
+    if weighting is not None:
+        wreq = _user_request_weighted(user_id, weighting)
+        if wreq is None:
+            return []
+        liked, rated, w = wreq
+        scores, rows = score_topk(movies_collab_catalog, k, liked=[liked], exclude=[rated],
+                                  liked_weights=[w],
+                                  allow=_allow_of(allow) if allow is not None else None)
+        return _hydrate(scores[0].cpu().numpy(), rows[0].cpu().numpy())
     req = _user_request(user_id)
     if req is None:
         return []
@@ -162,12 +212,21 @@ def get_user_recs(user_id: str, k: int = 10, allow=None) -> List[Recommendation]
 get_user_recs_gpu = get_user_recs  # SURVEY §8b's name for the drop-in
 
 
-def get_user_recs_batched(batcher, user_id: str, k: int = 10,
-                          allow=None) -> List[Recommendation]:
+def get_user_recs_batched(batcher, user_id: str, k: int = 10, allow=None,
+                          weighting: Optional[Callable[[float], float]] = None
+                          ) -> List[Recommendation]:
     """``get_user_recs`` whose scoring step is coalesced with concurrent callers by a
     ``batcher.RecBatcher`` over ``movies_collab_catalog``: same SQL, same errors,
     same ordering; the GPU sees one batch for many request threads. allow: a mask index or name
-    of the batcher's ``allow_masks`` (None: unfiltered)."""
+    of the batcher's ``allow_masks`` (None: unfiltered). weighting: as ``get_user_recs``'s."""
+    if weighting is not None:
+        wreq = _user_request_weighted(user_id, weighting)
+        if wreq is None:
+            return []
+        liked, rated, w = wreq
+        kw = {"allow": allow} if allow is not None else {}
+        s, r = batcher.submit(liked, rated, k, weights=w, **kw).result()
+        return _hydrate(s, r)
     req = _user_request(user_id)
     if req is None:
         return []

@@ -82,6 +82,9 @@ class SortedCSR(tuple):
     min_len = None
     row_min = None
     row_max = None
+    # set by csr_from_weighted_lists: the liked weights that go with this CSR were checked on
+    # the host too (finite, sum |w| > 0), as EBT_FLAG_LIKED_CHECKED then also vouches for
+    weights_checked = False
 
     def __new__(cls, off: torch.Tensor, rows: torch.Tensor, min_len=None, row_min=None,
                 row_max=None):
@@ -119,6 +122,94 @@ def csr_from_lists(lists: Sequence[Sequence[int]], device,
     return SortedCSR(t[:B + 1], t[B + 1:], min_len=int(lens.min()) if B else 0,
                      row_min=int(rows.min()) if nnz else None,
                      row_max=int(rows.max()) if nnz else None)
+
+
+def abs_weight_sums(off: np.ndarray, w: np.ndarray) -> np.ndarray:
+    """W_b = sum_l |w_l| of every CSR segment as the library computes it (ebert.h 0.8.0): a
+    sequential float64 sum in CSR order (np.cumsum adds left to right; np.sum pairs)."""
+    a = np.abs(np.asarray(w, dtype=np.float64))
+    return np.array([np.cumsum(a[s:e])[-1] if e > s else 0.0
+                     for s, e in zip(off[:-1], off[1:])], dtype=np.float64)
+
+
+def check_weights(off: np.ndarray, w: np.ndarray) -> np.ndarray:
+    """The library's host check of liked weights (every weight finite, W_b > 0), EbertError
+    naming the query; returns W [B]. Segments without rows are left to the liked path's own
+    check (sklearn's message)."""
+    w = np.asarray(w, dtype=np.float64)
+    off = np.asarray(off, dtype=np.int64)
+    W = abs_weight_sums(off, w)
+    # (a NaN or infinite weight makes its W_b NaN or infinite: one vector test clears a good batch)
+    if not ((off[1:] > off[:-1]) & ~((W > 0.0) & np.isfinite(W))).any():
+        return W
+    for b in range(len(off) - 1):
+        s, e = int(off[b]), int(off[b + 1])
+        if e <= s:
+            continue
+        if not np.isfinite(w[s:e]).all():
+            raise EbertError(f"liked weights of query {b} are not all finite")
+        if not (W[b] > 0.0 and np.isfinite(W[b])):
+            raise EbertError(f"liked weights of query {b} sum to |w| = {W[b]} "
+                             "(a finite sum > 0 is required)")
+    return W
+
+
+def csr_from_weighted_lists(lists: Sequence[Sequence[int]], weights: Sequence[Sequence[float]],
+                            device, stager=None, check: bool = True
+                            ) -> Tuple[SortedCSR, torch.Tensor]:
+    """csr_from_lists for liked rows with one weight per entry (ebert.h 0.8.0): the same CSR,
+    and the weights as a device float64 [nnz] in the CSR's order (each list is sorted by row,
+    stably, and its weights move with it). Checked here, EbertError naming the query: a weights
+    list of another length than its liked list, a non-finite weight, sum |w| == 0. The CSR's
+    ``weights_checked`` is set: with ``checked_for`` the C entry reads nothing back."""
+    if len(weights) != len(lists):
+        raise EbertError(f"{len(weights)} weight lists for {len(lists)} liked lists")
+    segs, ws = [], []
+    for b, (l, w) in enumerate(zip(lists, weights)):
+        r = np.asarray(l, dtype=np.int64).ravel()
+        try:
+            x = np.asarray(w, dtype=np.float64).ravel()
+        except (TypeError, ValueError) as e:
+            raise EbertError(f"liked weights of query {b}: {e}") from None
+        if x.size != r.size:
+            raise EbertError(f"query {b} has {x.size} weights for {r.size} liked rows")
+        o = np.argsort(r, kind="stable")
+        segs.append(r[o])
+        ws.append(x[o])
+    csr = csr_from_lists(segs, device, stager)   # (sorted already: np.sort leaves them as they are)
+    flat = np.concatenate(ws) if ws else np.zeros(0)
+    off = np.zeros(len(segs) + 1, dtype=np.int64)
+    np.cumsum([s.size for s in segs], out=off[1:])
+    if check:   # (check=False: a shard's part of the lists, whose W_b the caller checked whole)
+        check_weights(off, flat)
+    wt = torch.from_numpy(flat if flat.size else np.zeros(1)).to(device)
+    csr.weights_checked = bool(check)
+    return csr, wt
+
+
+def _liked_with_weights(liked, liked_weights, dev):
+    """(liked CSR, device weights or None) of score_topk's liked= / liked_weights=: host lists
+    of lists parallel to host liked lists, or a device float64 [nnz] tensor for a CSR pair."""
+    if liked_weights is None:
+        return (liked if isinstance(liked, tuple) or liked is None
+                else csr_from_lists(liked, dev)), None
+    if liked is None:
+        raise EbertError("liked_weights= weighs liked rows: pass liked= (dense queries take none)")
+    if isinstance(liked, tuple):
+        if not isinstance(liked_weights, torch.Tensor):
+            raise EbertError("with a device CSR, liked_weights must be a device float64 [nnz] "
+                             "tensor")
+        require_cuda(liked_weights, "liked_weights")
+        if liked_weights.dtype != torch.float64 or liked_weights.dim() != 1 \
+                or liked_weights.numel() != liked[1].numel():
+            raise EbertError(f"liked_weights must be float64 [{int(liked[1].numel())}] (one per "
+                             f"liked row), got {liked_weights.dtype} "
+                             f"{tuple(liked_weights.shape)}")
+        return liked, liked_weights.contiguous()
+    if isinstance(liked_weights, torch.Tensor):
+        raise EbertError("with host liked lists, liked_weights must be host lists parallel to "
+                         "them")
+    return csr_from_weighted_lists(liked, liked_weights, dev)
 
 
 def csr_sorted(off, rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -165,7 +256,8 @@ def csr_subset(off: torch.Tensor, rows: torch.Tensor, idx: torch.Tensor):
 def prepare_queries(catalog: Catalog, queries: Optional[torch.Tensor] = None,
                     liked: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                     liked_counts: Optional[torch.Tensor] = None,
-                    liked_sum_hook=None) -> QueryBatch:
+                    liked_sum_hook=None, liked_weights: Optional[torch.Tensor] = None,
+                    liked_wsum: Optional[torch.Tensor] = None) -> QueryBatch:
     """Build q64 / qimg / qscale / eps for a batch.
 
     queries : dense [B, d] CUDA tensor (any supported dtype), or
@@ -173,6 +265,11 @@ def prepare_queries(catalog: Catalog, queries: Optional[torch.Tensor] = None,
               sum_l x_l/||x_l|| divided by liked_counts (default: the CSR lengths). liked_sum_hook,
               if given, is applied to the float64 sums before the division (the cross-shard
               all-reduce of a row-sharded catalog).
+    liked_weights : device float64 [nnz], one weight per liked row in the CSR's order (ebert.h
+              0.8.0): the query is sum_l w_l x_l/||x_l|| (ebt_query_liked_wsum) divided by
+              liked_wsum, the weighted twin of liked_counts: float64 [B], each query's
+              W_b = sum |w_l| over its WHOLE list (a shard's CSR holds only its own rows).
+              Default: the CSR's own sums, computed and checked on the host as the C entry does.
     """
     dev = catalog.device
     st = stream_of(dev)
@@ -208,8 +305,18 @@ def prepare_queries(catalog: Catalog, queries: Optional[torch.Tensor] = None,
         B = int(off.numel()) - 1
         q64 = torch.empty((B, d), dtype=torch.float64, device=dev)
         local = rows - catalog.row_offset if catalog.row_offset else rows
-        call("ebt_query_liked_sum", ptr(catalog.data), catalog.dtype_code, d, catalog.ld,
-             ptr(catalog.gnorm), B, ptr(off), ptr(local), ptr(q64), st)
+        if liked_weights is None:
+            if liked_wsum is not None:
+                raise EbertError("liked_wsum= goes with liked_weights=")
+            call("ebt_query_liked_sum", ptr(catalog.data), catalog.dtype_code, d, catalog.ld,
+                 ptr(catalog.gnorm), B, ptr(off), ptr(local), ptr(q64), st)
+        else:
+            require_cuda(liked_weights, "liked_weights")
+            if liked_weights.dtype != torch.float64 or liked_weights.numel() < rows.numel():
+                raise EbertError("liked_weights must be float64, one per liked row")
+            liked_weights = liked_weights.contiguous()
+            call("ebt_query_liked_wsum", ptr(catalog.data), catalog.dtype_code, d, catalog.ld,
+                 ptr(catalog.gnorm), B, ptr(off), ptr(local), ptr(liked_weights), ptr(q64), st)
         if liked_sum_hook is not None:
             q64 = liked_sum_hook(q64)
         counts = liked_counts if liked_counts is not None else (off[1:] - off[:-1])
@@ -217,7 +324,16 @@ def prepare_queries(catalog: Catalog, queries: Optional[torch.Tensor] = None,
             raise ValueError(
                 f"Found array with 0 sample(s) (shape=(0, {d})) while a minimum of 1 is required "
                 "by check_pairwise_arrays.")
-        scale = (1.0 / counts.to(torch.float64)).contiguous()
+        if liked_weights is None:
+            scale = (1.0 / counts.to(torch.float64)).contiguous()
+        elif liked_wsum is not None:
+            wsum = liked_wsum.to(device=dev, dtype=torch.float64)
+            if wsum.shape != (B,) or not bool((torch.isfinite(wsum) & (wsum > 0)).all().item()):
+                raise EbertError("liked_wsum must be float64 [B], finite and > 0")
+            scale = (1.0 / wsum).contiguous()
+        else:   # the C entry's host check and its sequential W_b, so the same bits
+            W = check_weights(off.cpu().numpy(), liked_weights.cpu().numpy())
+            scale = torch.from_numpy(1.0 / W).to(dev)
         call("ebt_scale_rows_f64", ptr(q64), B, d, ptr(scale), st)
     B_pad = pad_batch(B)
     qimg = torch.empty((B_pad, catalog.ld_img), dtype=catalog.img_torch_dtype, device=dev)
@@ -420,7 +536,8 @@ def score_topk_submit(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
                kprime: Optional[int] = None, chunk_rows: Optional[int] = None,
                timer: Optional[_lib.Timer] = None, liked_counts: Optional[torch.Tensor] = None,
                liked_sum_hook=None, fuse: bool = True,
-               t_floor_hook=None, theta_hook=None, allow=None) -> "PendingTopk":
+               t_floor_hook=None, theta_hook=None, allow=None, liked_weights=None,
+               liked_wsum: Optional[torch.Tensor] = None) -> "PendingTopk":
     """Enqueue the first pass of score_topk (see there) on the catalog's device and return
     without waiting for it: score_topk_finish(pending) waits, retries the queries whose
     certificate needs it and returns (scores, rows). Submitting batch i+1 before finishing
@@ -462,26 +579,40 @@ def score_topk_submit(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
     and the others (unfiltered, or masks without one) run as one sub-batch as described above.
     The returned pending's ``routes`` lists (mask, query indices, sub-catalog rows) of every such
     group (empty when none). A device tensor of ids always takes the mask pass.
+
+    liked_weights (with liked=; include/ebert.h 0.8.0): one float64 weight per liked row -- host
+    lists of lists parallel to host ``liked`` lists, or a device float64 [nnz] tensor for a
+    device CSR pair, in the CSR's order. The score of row j is sum_l w_l cos(x_l, x_j) / sum_l
+    |w_l|; negative weights push away, duplicates in a liked list are separate terms. None is
+    the unweighted call, kernel for kernel. All weights 1.0 give its bits; so does any power of
+    two times the weights; a 0.0 weight is that entry removed. Errors (EbertError naming the
+    query, before any scoring): a weights list of another length than its liked list, a
+    non-finite weight, sum |w| == 0. liked_wsum (row-sharded catalogs, with liked_counts): each
+    query's sum |w| over its whole list, the weighted twin of liked_counts.
     """
+    if liked_weights is not None and liked is None:
+        raise EbertError("liked_weights= weighs liked rows: pass liked= (dense queries take none)")
     if allow is not None:
         if t_floor_hook is not None or theta_hook is not None or liked_sum_hook is not None \
-                or liked_counts is not None:
+                or liked_counts is not None or liked_wsum is not None:
             raise EbertError("allow= is not supported with t_floor_hook / theta_hook / "
                              "liked_sum_hook (row-sharded catalogs take no allow masks)")
         routed = _submit_routed(catalog, k, queries, liked, exclude, kprime, chunk_rows, timer,
-                                fuse, allow)
+                                fuse, allow, liked_weights)
         if routed is not None:
             return routed
         return _submit_c(catalog, k, queries, liked, exclude, kprime, chunk_rows, timer, fuse,
-                         allow)
+                         allow, liked_weights)
     if t_floor_hook is None and theta_hook is None and liked_sum_hook is None and \
-            liked_counts is None:
+            liked_counts is None and liked_wsum is None:
         # one catalog (or a shard queried on its own): the C ABI's self-contained path
-        return _submit_c(catalog, k, queries, liked, exclude, kprime, chunk_rows, timer, fuse)
+        return _submit_c(catalog, k, queries, liked, exclude, kprime, chunk_rows, timer, fuse,
+                         None, liked_weights)
     g = score_topk_stages(catalog, k, queries=queries, liked=liked, exclude=exclude,
                           kprime=kprime, chunk_rows=chunk_rows, timer=timer,
                           liked_counts=liked_counts, liked_sum_hook=liked_sum_hook, fuse=fuse,
-                          t_floor_hook=t_floor_hook, theta_hook=theta_hook)
+                          t_floor_hook=t_floor_hook, theta_hook=theta_hook,
+                          liked_weights=liked_weights, liked_wsum=liked_wsum)
     next(g)
     next(g)
     return next(g)
@@ -507,15 +638,19 @@ _SKLEARN_EMPTY = "Found array with 0 sample(s)"
 
 
 def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_rows, timer,
-              fuse, allow=None) -> PendingTopkC:
+              fuse, allow=None, liked_weights=None) -> PendingTopkC:
     """score_topk_submit over ebt_cosine_topk_submit: query prep, the screen, the certificate
-    and every retry run inside libebert (include/ebert.h); Python only owns the buffers."""
+    and every retry run inside libebert (include/ebert.h); Python only owns the buffers.
+    With liked_weights the entry is ebt_cosine_topk_weighted_submit (finished like the others)."""
     import ctypes
     if k < 1:
         raise EbertError("k must be >= 1")
     dev = catalog.device
     if (queries is None) == (liked is None):
         raise EbertError("pass exactly one of queries= or liked=")
+    lw = None
+    if liked_weights is not None:
+        liked, lw = _liked_with_weights(liked, liked_weights, dev)
     if exclude is not None:
         exclude = (csr_from_lists(exclude, dev) if not isinstance(exclude, tuple)
                    else exclude if isinstance(exclude, SortedCSR) else csr_sorted(*exclude))
@@ -542,7 +677,8 @@ def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_r
     if ra is not None:   # a filtered batch is unfused: the workspace is sized with the flag
         flags |= _lib.EBT_FLAG_NO_FUSE
     if liked is not None and isinstance(lo_csr, SortedCSR) and lo_csr.checked_for(
-            catalog.row_offset, catalog.row_offset + catalog.n):
+            catalog.row_offset, catalog.row_offset + catalog.n) and (
+                lw is None or lo_csr.weights_checked):
         # checked on the host while building it: the C entry reads nothing back (no stream sync)
         flags |= _lib.EBT_FLAG_LIKED_CHECKED
     opt = _lib.EbtOptions(kprime=int(kprime or 0), flags=flags, chunk_rows=int(chunk_rows or 0))
@@ -561,7 +697,10 @@ def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_r
             ptr(er), ctypes.byref(opt), ptr(ws), need, ptr(out_s), ptr(out_r), ptr(cert_host),
             ctypes.byref(pend), timer.handle if timer is not None else None, stream_of(dev))
     try:
-        if ra is None:
+        if lw is not None:
+            call("ebt_cosine_topk_weighted_submit", *args,
+                 ctypes.byref(ra[0]) if ra is not None else None, ptr(lw))
+        elif ra is None:
             call("ebt_cosine_topk_submit", *args)
         else:
             call("ebt_cosine_topk_allowed_submit", *args, ctypes.byref(ra[0]))
@@ -571,7 +710,7 @@ def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_r
             raise ValueError(msg[msg.index(_SKLEARN_EMPTY):]) from None
         raise
     return PendingTopkC(pend, catalog, opt, out_s, out_r, ws, cert_host,
-                        (queries, lo, lr, eo, er) + (ra[1] if ra is not None else ()),
+                        (queries, lo, lr, lw, eo, er) + (ra[1] if ra is not None else ()),
                         ra[0] if ra is not None else None)
 
 
@@ -615,12 +754,13 @@ def _sub_exclusions(masks, mask: int, sub, exclude, B: int, dev) -> Optional[Sor
 
 
 def _submit_liked_on_view(parent: Catalog, view: Catalog, k: int, liked, exclude, kprime,
-                          chunk_rows, timer, fuse) -> "PendingTopk":
+                          chunk_rows, timer, fuse, liked_weights=None) -> "PendingTopk":
     """Liked queries over a sub-catalog: the queries are prepared on the PARENT (liked rows need
     not be allowed; the image and eps use the parent's u_cat, which the view carries), the first
-    pass runs the prepared entry over the view; score_topk_finish's retry loop completes it."""
+    pass runs the prepared entry over the view; score_topk_finish's retry loop completes it.
+    liked_weights: as score_topk_submit's (the weighted sum and 1 / sum |w| on the parent)."""
     dev = parent.device
-    lo = liked if isinstance(liked, tuple) else csr_from_lists(liked, dev)
+    lo, lw = _liked_with_weights(liked, liked_weights, dev)
     if not (isinstance(lo, SortedCSR) and lo.row_min is not None
             and lo.row_min >= 0 and lo.row_max < parent.n):
         o0, o1 = int(lo[0][0].item()), int(lo[0][-1].item())
@@ -628,7 +768,7 @@ def _submit_liked_on_view(parent: Catalog, view: Catalog, k: int, liked, exclude
         if seg.numel() and bool(((seg < 0) | (seg >= parent.n)).any().item()):
             raise EbertError(f"liked rows must be in the catalog rows [0, {parent.n})")
     with region(timer, "prep", dev):
-        qb = prepare_queries(parent, liked=lo)
+        qb = prepare_queries(parent, liked=lo, liked_weights=lw)
     n_cap = _round_up(view.n, 4)
     k_eff = min(k, view.n)
     if k_eff > KPRIME_MAX:
@@ -645,8 +785,27 @@ def _submit_liked_on_view(parent: Catalog, view: Catalog, k: int, liked, exclude
                        cert, cert_host, ready, None)
 
 
+def _take_weights(liked, weights, idx_host, idx_dev):
+    """The liked weights that go with _take(liked, ...): host lists, or the device tensor's
+    entries of the queries idx in the subset CSR's order."""
+    if weights is None:
+        return None
+    if isinstance(liked, tuple) and isinstance(weights, torch.Tensor):
+        if weights.numel() != liked[1].numel():
+            raise EbertError(f"liked_weights must be float64 [{int(liked[1].numel())}]")
+        off, w = csr_subset(liked[0], weights, idx_dev)
+        return w if int(off[-1].item()) else torch.zeros(1, dtype=torch.float64,
+                                                         device=weights.device)
+    if isinstance(liked, tuple) or isinstance(weights, torch.Tensor):
+        raise EbertError("liked_weights: host lists go with host liked lists, a device tensor "
+                         "with a device CSR")
+    if len(weights) != len(liked):
+        raise EbertError(f"{len(weights)} weight lists for {len(liked)} liked lists")
+    return [weights[b] for b in idx_host]
+
+
 def _submit_routed(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_rows, timer,
-                   fuse, allow) -> Optional[PendingRouted]:
+                   fuse, allow, liked_weights=None) -> Optional[PendingRouted]:
     """score_topk_submit's routing of a filtered batch over materialised masks
     (AllowMasks.materialize). Only for a HOST list of mask ids: a device tensor would have to be
     read back. Returns None -- the batch takes the mask pass as a whole -- when no query's mask
@@ -690,7 +849,8 @@ def _submit_routed(catalog: Catalog, k: int, queries, liked, exclude, kprime, ch
                           chunk_rows, timer, fuse)
         else:
             p = _submit_liked_on_view(catalog, sub.catalog, k, _take(liked, qs, idx), ex, kprime,
-                                      chunk_rows, timer, fuse)
+                                      chunk_rows, timer, fuse,
+                                      _take_weights(liked, liked_weights, qs, idx))
         parts.append((idx, p, sub))
         routes.append((m, list(qs), sub.m))
         taken.update(qs)
@@ -700,7 +860,8 @@ def _submit_routed(catalog: Catalog, k: int, queries, liked, exclude, kprime, ch
         rest_ids = [host[b] for b in rest]
         p = _submit_c(catalog, k, queries.index_select(0, idx) if queries is not None else None,
                       _take(liked, rest, idx), _take(exclude, rest, idx), kprime, chunk_rows,
-                      timer, fuse, (masks, rest_ids) if any(i >= 0 for i in rest_ids) else None)
+                      timer, fuse, (masks, rest_ids) if any(i >= 0 for i in rest_ids) else None,
+                      _take_weights(liked, liked_weights, rest, idx))
         parts.append((idx, p, None))
     return PendingRouted(catalog, B, k, parts, tuple(routes))
 
@@ -724,17 +885,24 @@ def score_topk_stages(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
                       liked=None, exclude=None, kprime: Optional[int] = None,
                       chunk_rows: Optional[int] = None, timer: Optional[_lib.Timer] = None,
                       liked_counts: Optional[torch.Tensor] = None, liked_sum_hook=None,
-                      fuse: bool = True, t_floor_hook=None, theta_hook=None):
+                      fuse: bool = True, t_floor_hook=None, theta_hook=None,
+                      liked_weights=None, liked_wsum: Optional[torch.Tensor] = None):
     """score_topk_submit as a generator of three stages, so a caller can interleave the stages
     of consecutive batches (distributed.py: each stage of a row-sharded batch ends in a
     collective, and the next stage of the OTHER batch runs while it is in flight):
       next() #1: query prep and theta_hook (the shared threshold's all-gather);
       next() #2: the screen and t_floor_hook (the floor's all-gather);
       next() #3: the rescore; returns the PendingTopk (score_topk_finish completes it).
-    Without t_floor_hook the whole first pass runs in stage 2."""
+    Without t_floor_hook the whole first pass runs in stage 2.
+    liked_weights / liked_wsum: as score_topk_submit's."""
     if k < 1:
         raise EbertError("k must be >= 1")
     dev = catalog.device
+    lw = None
+    if liked_weights is not None:
+        liked, lw = _liked_with_weights(liked, liked_weights, dev)
+    elif liked_wsum is not None:
+        raise EbertError("liked_wsum= goes with liked_weights=")
     if liked is not None and not isinstance(liked, tuple):
         liked = csr_from_lists(liked, dev)
     if exclude is not None:
@@ -744,7 +912,8 @@ def score_topk_stages(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
         raise EbertError("theta_hook needs t_floor_hook (the threshold is verified against it)")
     with region(timer, "prep", dev):
         qb = prepare_queries(catalog, queries=queries, liked=liked, liked_counts=liked_counts,
-                             liked_sum_hook=liked_sum_hook)
+                             liked_sum_hook=liked_sum_hook, liked_weights=lw,
+                             liked_wsum=liked_wsum)
     n_cap = _round_up(catalog.n, 4)
     k_eff = min(k, catalog.n)
     if k_eff > KPRIME_MAX:
@@ -843,14 +1012,17 @@ def score_topk(catalog: Catalog, k: int, queries: Optional[torch.Tensor] = None,
                timer: Optional[_lib.Timer] = None, liked_counts: Optional[torch.Tensor] = None,
                liked_sum_hook=None, fuse: bool = True,
                t_floor_hook=None, theta_hook=None,
-               allow=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Top-k by cosine (mean cosine over liked rows) with exclusions: score_topk_submit +
-    score_topk_finish (arguments and results as documented there)."""
+               allow=None, liked_weights=None,
+               liked_wsum: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k by cosine (mean cosine over liked rows, or their weighted mean with
+    liked_weights=) with exclusions: score_topk_submit + score_topk_finish (arguments and
+    results as documented there)."""
     return score_topk_finish(score_topk_submit(
         catalog, k, queries=queries, liked=liked, exclude=exclude, kprime=kprime,
         chunk_rows=chunk_rows, timer=timer, liked_counts=liked_counts,
         liked_sum_hook=liked_sum_hook, fuse=fuse, t_floor_hook=t_floor_hook,
-        theta_hook=theta_hook, allow=allow))
+        theta_hook=theta_hook, allow=allow, liked_weights=liked_weights,
+        liked_wsum=liked_wsum))
 
 
 @dataclass
