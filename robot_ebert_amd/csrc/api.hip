@@ -107,16 +107,6 @@ constexpr int64_t PILOT_ROWS = 1024;  // = WMERGE_H (select_topk.hip)
 // The host-only types of this file are file-local (internal.h: the linkage rule)
 namespace {
 
-// EBT_FLAG_EXACT screening operands (the float64 catalog path), null for the MFMA screen
-struct ExactScreen {
-  const double* q64;
-  int32_t d;
-  const void* cat;
-  int dtype;
-  int64_t ld;
-  const double* gnorm;
-};
-
 // ------------------------------------------------------------------------------ timer ------
 struct Timer {
   struct Rec {
@@ -549,14 +539,16 @@ static WsLayout ws_layout(int64_t B, int64_t B_pad, int64_t n_rows, int32_t kpri
 }
 
 // Top-k' of rows [r0, r0+nrows) of the (shard-local) catalog into dv/di (row stride ld_d), the
-// unfused way: chunked GEMM -> mask -> streaming select (-> select across chunks).
-static int head_topk(const WsLayout& L, char* ws, const void* qimg, const float* qscale,
-                     int64_t B, int64_t B_pad, const void* cimg, const float* cscale,
-                     int img_dtype, int32_t ld_img, int64_t r0, int64_t nrows, int32_t d_pad,
-                     int64_t row_offset, const int64_t* excl_off, const int64_t* excl_rows,
-                     int32_t kprime, float* dv_final, int64_t* di_final, int64_t ld_final,
-                     void* timer, hipStream_t st, const ExactScreen* ex = nullptr,
-                     const ebt_allow* allow = nullptr) {
+// unfused way: chunked GEMM (EBT_FLAG_EXACT: the float64 screen of the catalog rows themselves)
+// -> mask -> streaming select (-> select across chunks).
+static int head_topk(const PipeArgs& a, const WsLayout& L, char* ws, int64_t r0, int64_t nrows,
+                     float* dv_final, int64_t* di_final, int64_t ld_final, void* timer,
+                     hipStream_t st) {
+  const QueryOps& q = a.q;
+  const CatOps& c = a.c;
+  const int64_t B = q.B, row_offset = c.row_offset;
+  const int32_t kprime = a.kprime;
+  const bool exact = a.flags & EBT_FLAG_EXACT;
   float* S = (float*)(ws + L.off_s);
   float* segv = (float*)(ws + L.off_segv);
   int64_t* segi = (int64_t*)(ws + L.off_segi);
@@ -564,33 +556,34 @@ static int head_topk(const WsLayout& L, char* ws, const void* qimg, const float*
   int64_t* chi = (int64_t*)(ws + L.off_chi);
   const int64_t n_chunks = ceil_div(nrows, L.chunk);
   int rc;
-  for (int64_t c = 0; c < n_chunks; ++c) {
-    const int64_t c0 = r0 + c * L.chunk;
+  for (int64_t ch = 0; ch < n_chunks; ++ch) {
+    const int64_t c0 = r0 + ch * L.chunk;
     const int64_t nc = (r0 + nrows - c0) < L.chunk ? (r0 + nrows - c0) : L.chunk;
     {
       StageScope s(timer, EBT_STAGE_GEMM, st);
-      if (ex) {
-        const int es = ex->dtype == EBT_F64 ? 8 : (ex->dtype == EBT_F32 ? 4 : 2);
-        rc = screen_exact(ex->q64, B, ex->d, (const char*)ex->cat + c0 * ex->ld * es, ex->dtype,
-                          ex->ld, ex->gnorm + c0, nc, S, L.ld_s, st);
+      if (exact) {
+        const int es = c.dtype == EBT_F64 ? 8 : (c.dtype == EBT_F32 ? 4 : 2);
+        rc = screen_exact(q.q64, B, c.d, (const char*)c.cat + c0 * c.ld * es, c.dtype, c.ld,
+                          c.gnorm64 + c0, nc, S, L.ld_s, st);
       } else {
-        rc = screen_gemm(qimg, B_pad, (const char*)cimg + c0 * ld_img * 2, nc, d_pad, ld_img,
-                         img_dtype, qscale, cscale ? cscale + c0 : nullptr, S, L.ld_s, st);
+        rc = screen_gemm(q.qimg, q.B_pad, (const char*)c.cimg + c0 * c.ld_img * 2, nc, c.d_pad,
+                         c.ld_img, c.img_dtype, q.qscale, c.cscale ? c.cscale + c0 : nullptr, S,
+                         L.ld_s, st);
       }
     }
     if (rc) return rc;
-    if (excl_off || allow) {
+    if (a.excl.off || a.allow) {
       StageScope s(timer, EBT_STAGE_MASK, st);
-      rc = excl_off ? mask_excluded(S, L.ld_s, B, row_offset + c0, row_offset + c0 + nc,
-                                    excl_off, excl_rows, st)
-                    : EBT_OK;
+      rc = a.excl.off ? mask_excluded(S, L.ld_s, B, row_offset + c0, row_offset + c0 + nc,
+                                      a.excl.off, a.excl.rows, st)
+                      : EBT_OK;
       // per-query allow masks (allow_mask.hip): the rows a filtered query may not see
-      if (!rc && allow)
-        rc = mask_allowed(S, L.ld_s, B, row_offset + c0, row_offset + c0 + nc, allow, st);
+      if (!rc && a.allow)
+        rc = mask_allowed(S, L.ld_s, B, row_offset + c0, row_offset + c0 + nc, a.allow, st);
       if (rc) return rc;
     }
-    float* dv = n_chunks == 1 ? dv_final : chv + c * kprime;
-    int64_t* di = n_chunks == 1 ? di_final : chi + c * kprime;
+    float* dv = n_chunks == 1 ? dv_final : chv + ch * kprime;
+    int64_t* di = n_chunks == 1 ? di_final : chi + ch * kprime;
     const int64_t ld_d = n_chunks == 1 ? ld_final : n_chunks * kprime;
     {
       StageScope s(timer, EBT_STAGE_SELECT, st);
@@ -619,17 +612,12 @@ static int head_topk(const WsLayout& L, char* ws, const void* qimg, const float*
 // (list_base = row_offset: no local-rows pass), and the certificate also takes ebt_certify_cut's
 // tests (an overflowed fused list, a caller's threshold above the floor's cut) -- two launches
 // fewer per step. Timed and row-counted as ebt_rescore.
-int rescore_sharded(const double* q64, int64_t B, int32_t d, const void* cat, int dtype,
-                    int64_t ld, const double* gnorm64, int64_t row_offset, const float* cand_vals,
-                    const int64_t* cand_rows, int32_t kprime, int32_t k, int64_t n_rows,
+int rescore_sharded(const double* q64, int64_t B, const CatOps& c, const CandList& l, int32_t k,
                     const float* eps, const double* t_floor, double* out_s, int64_t* out_r,
-                    int32_t* certified, const int* ovf, const float* theta, void* timer,
-                    hipStream_t st, int64_t list_base, const int64_t* excl_off,
-                    const int64_t* excl_rows, const ShardPackOut* pack) {
+                    int32_t* certified, RescoreExtras x, void* timer, hipStream_t st) {
   StageScope sc(timer, EBT_STAGE_RESCORE, st);
-  return rescore(q64, B, d, cat, dtype, ld, gnorm64, row_offset, cand_vals, cand_rows,
-                 kprime, k, n_rows, eps, t_floor, out_s, out_r, certified, st, ovf, 0,
-                 timer_rows(timer, st), list_base, theta, excl_off, excl_rows, pack);
+  x.gathered = timer_rows(timer, st);
+  return rescore(q64, B, c, l, k, eps, t_floor, out_s, out_r, certified, x, st);
 }
 
 }  // namespace ebt
@@ -663,7 +651,7 @@ int ebt_query_liked_sum(const void* cat, int dtype, int32_t d, int64_t ld,
                         const double* gnorm64_cat, int64_t B, const int64_t* liked_off,
                         const int64_t* liked_rows, double* q64, void* stream) {
   return query_liked_sum(cat, dtype, d, ld, gnorm64_cat, B, liked_off, liked_rows, q64,
-                         (hipStream_t)stream);
+                         (hipStream_t)stream, 0, 0);
 }
 
 int ebt_query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld,
@@ -671,7 +659,7 @@ int ebt_query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld,
                          const int64_t* liked_rows, const double* liked_w, double* q64,
                          void* stream) {
   return query_liked_wsum(cat, dtype, d, ld, gnorm64_cat, B, liked_off, liked_rows, liked_w, q64,
-                          (hipStream_t)stream);
+                          (hipStream_t)stream, 0, 0);
 }
 
 int ebt_query_prep(const void* q, int dtype, int64_t B, int64_t B_pad, int32_t d, int64_t ldq,
@@ -734,10 +722,12 @@ int ebt_rescore(const double* q64, int64_t B, int32_t d, const void* cat, int dt
                 const int64_t* cand_rows, int32_t kprime, int32_t k, int64_t n_rows, const float* eps,
                 const double* t_floor, double* out_scores, int64_t* out_rows, int32_t* certified,
                 void* timer, void* stream) {
-  StageScope sc(timer, EBT_STAGE_RESCORE, (hipStream_t)stream);
-  return rescore(q64, B, d, cat, dtype, ld, gnorm64, row_offset, cand_vals, cand_rows, kprime, k,
-                 n_rows, eps, t_floor, out_scores, out_rows, certified, (hipStream_t)stream,
-                 nullptr, 0, timer_rows(timer, (hipStream_t)stream));
+  hipStream_t st = (hipStream_t)stream;
+  StageScope sc(timer, EBT_STAGE_RESCORE, st);
+  const CatOps c{cat, dtype, ld, gnorm64, nullptr, nullptr, 0, 0, n_rows, d, 0, row_offset};
+  const RescoreExtras x{nullptr, nullptr, {}, nullptr, timer_rows(timer, st)};
+  return rescore(q64, B, c, {cand_vals, cand_rows, kprime, 0}, k, eps, t_floor, out_scores,
+                 out_rows, certified, x, st);
 }
 
 int ebt_screen_exact(const double* q64, int64_t B, int32_t d, const void* cat, int dtype,
@@ -761,11 +751,13 @@ int ebt_merge_hits(float* fv, int64_t* fi, int64_t B, int32_t kprime, int32_t k,
     return EBT_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
+  // (the merges only read the slots; the record is shared with the launches that fill them)
+  const HitSlots h{const_cast<uint64_t*>(cand), ld_cand, slots, const_cast<uint8_t*>(counts),
+                   ld_counts};
   if (merge_wave_fits(kprime) && n_groups <= merge_wave_max_groups() && ld_counts % 16 == 0)
-    return merge_segment_wave(fv, fi, B, kprime, k, cand, ld_cand, slots, counts, ld_counts,
-                              n_groups, row_offset, excl_off, excl_rows, ovf, st);
-  return merge_segment(fv, fi, B, kprime, cand, ld_cand, slots, counts, ld_counts, n_groups,
-                       row_offset, excl_off, excl_rows, ovf, st);
+    return merge_segment_wave(fv, fi, B, kprime, k, h, n_groups, row_offset,
+                              {excl_off, excl_rows}, ovf, st);
+  return merge_segment(fv, fi, B, kprime, h, n_groups, row_offset, {excl_off, excl_rows}, ovf, st);
 }
 
 int ebt_merge_topk(const double* scores, const int64_t* rows, int32_t R, int64_t B, int32_t k,
@@ -828,74 +820,35 @@ int ebt_spec_lead(int on) {
 namespace ebt {
 namespace {
 
-// What the rescore needs from the screen: the eps the certificate uses (the caller's, or the
-// exact screen's constant) and the fused screen's overflow flags (null when not fused).
+// What an entry's tail needs from the screen: the list it filled, the eps the certificate uses
+// (the caller's, or the exact screen's constant), the fused screen's overflow flags (null when
+// not fused) and where the speculative screen keeps its threshold.
 struct ScreenOut {
+  float* fv;
+  int64_t* fi;
   const float* eps;
   const int* ovf;
-};
-
-struct PipeArgs {
-  const double* q64;
-  const void* qimg;
-  const float* qscale;
-  const float* eps;
-  int64_t B, B_pad;
-  const void* cat;
-  int dtype;
-  int64_t ld;
-  const double* gnorm64;
-  const void* cimg;
-  const float* cscale;
-  int img_dtype;
-  int32_t ld_img;
-  int64_t n_rows;
-  int32_t d, d_pad;
-  int64_t row_offset;
-  const int64_t* excl_off;
-  const int64_t* excl_rows;
-  int32_t k, kprime;
-  int64_t chunk_rows;
-  int flags;
-  // ebt_cosine_screen_at: the caller's per-query threshold [B] and expected hits per query
-  const float* theta = nullptr;
-  double hits = 0.0;
-  // ebt_cosine_screen_at_lead: the caller's sample lead -- the shard's first `lead` 256-row tiles,
-  // their scores [B_pad][ld_lead] stored by ebt_cosine_sample_lead
-  int64_t lead = 0;
-  const float* lead_s = nullptr;
-  int64_t ld_lead = 0;
-  // screen_at_local: the threshold as the gs_j-th of the all-gathered sample maxima ([R][B][gj],
-  // rank stride gs_rstride floats, gs_G values per query), taken by the same launch that starts
-  // the list and takes the lead's hits (instead of a caller's theta)
-  const float* gsamp = nullptr;
-  int64_t gs_rstride = 0;
-  int gs_G = 0, gs_gj = 0, gs_j = 0;
-  // screen_at_local: the row-sharded step's floor entries ([B][floor_w + 1], ebt_floor_pack's
-  // layout) written by the screen's last wave merge
-  float* floor_out = nullptr;
-  int floor_w = 0;
-  // ebt_cosine_topk_prepared_allowed: the per-query allow masks (unfused and float64 screens
-  // only: the entry sets EBT_FLAG_NO_FUSE), null = unfiltered
-  const ebt_allow* allow = nullptr;
+  const float* theta;
 };
 
 }  // namespace
 
 static int check_pipe(const PipeArgs& a, const char* who) {
+  const QueryOps& q = a.q;
+  const CatOps& c = a.c;
   const bool exact = a.flags & EBT_FLAG_EXACT;
-  if (!a.q64 || (!exact && (!a.qimg || !a.qscale || !a.eps || !a.cimg)) || !a.cat ||
-      !a.gnorm64) {
+  if (!q.q64 || (!exact && (!q.qimg || !q.qscale || !q.eps || !c.cimg)) || !c.cat ||
+      !c.gnorm64) {
     set_error("%s: null pointer", who);
     return EBT_EINVAL;
   }
-  if (a.B < 1 || a.B_pad < a.B || a.B_pad % 128 != 0 || a.n_rows < 1 || a.d < 1 ||
-      a.d_pad < a.d || a.d_pad % 64 != 0 || a.ld_img < a.d_pad || a.k < 1 || a.kprime < a.k ||
+  if (q.B < 1 || q.B_pad < q.B || q.B_pad % 128 != 0 || c.n_rows < 1 || c.d < 1 ||
+      c.d_pad < c.d || c.d_pad % 64 != 0 || c.ld_img < c.d_pad || a.k < 1 || a.kprime < a.k ||
       a.kprime > 4096 || a.kprime % 4 != 0 || a.chunk_rows < 128 || a.chunk_rows % 128 != 0 ||
-      ((a.excl_off == nullptr) != (a.excl_rows == nullptr))) {
+      ((a.excl.off == nullptr) != (a.excl.rows == nullptr))) {
     set_error("%s: bad arguments (B=%lld B_pad=%lld n=%lld d=%d d_pad=%d k=%d kprime=%d "
-              "chunk=%lld)", who, (long long)a.B, (long long)a.B_pad, (long long)a.n_rows, a.d,
-              a.d_pad, a.k, a.kprime, (long long)a.chunk_rows);
+              "chunk=%lld)", who, (long long)q.B, (long long)q.B_pad, (long long)c.n_rows, c.d,
+              c.d_pad, a.k, a.kprime, (long long)a.chunk_rows);
     return EBT_EINVAL;
   }
   return EBT_OK;
@@ -918,20 +871,22 @@ static int check_pipe(const PipeArgs& a, const char* who) {
 // One fused segment's filter screen over rows [r0, r0 + seg): one launch, or consecutive
 // launches of whole rounds when the segment is long (filter_split_rows, screen_gemm.hip), each
 // its own timed launch (the roofline's per-launch average stays a kernel's). The hits and counts
-// of group g of the segment land at cand + g * slots / counts + g, whatever the parts.
+// of group g of the segment land in group g of h, whatever the parts.
 static int filter_screen(const PipeArgs& a, int64_t r0, int64_t seg, const float* thr,
-                         uint64_t* cand, int64_t ld_cand, int slots, uint8_t* counts,
-                         int64_t ld_counts, int* ovf, void* timer, hipStream_t st) {
-  const int64_t part = filter_split_rows(a.B_pad, seg);
+                         const HitSlots& h, int* ovf, void* timer, hipStream_t st) {
+  const QueryOps& q = a.q;
+  const CatOps& c = a.c;
+  const int64_t part = filter_split_rows(q.B_pad, seg);
   const int64_t step = part > 0 ? part : seg;
   for (int64_t p0 = 0; p0 < seg; p0 += step) {
     const int64_t nr = seg - p0 < step ? seg - p0 : step;
-    const int64_t r = r0 + p0, g = p0 / 256;  // part boundaries are whole 256-row groups
+    const int64_t r = r0 + p0;
+    const HitSlots hp = from_group(h, p0 / 256);  // part boundaries are whole 256-row groups
     KernelStage s(timer, EBT_STAGE_GEMM_FILTER, st);
-    const int rc = screen_gemm_filter(a.qimg, a.B_pad, (const char*)a.cimg + r * a.ld_img * 2, nr,
-                                      a.d_pad, a.ld_img, a.img_dtype, a.qscale,
-                                      a.cscale ? a.cscale + r : nullptr, thr, cand + g * slots,
-                                      ld_cand, slots, counts + g, ld_counts, ovf, r, st);
+    const int rc = screen_gemm_filter(q.qimg, q.B_pad, (const char*)c.cimg + r * c.ld_img * 2, nr,
+                                      c.d_pad, c.ld_img, c.img_dtype, q.qscale,
+                                      c.cscale ? c.cscale + r : nullptr, thr, hp.cand, hp.ld_cand,
+                                      hp.slots, hp.counts, hp.ld_counts, ovf, r, st);
     if (rc) return rc;
   }
   return EBT_OK;
@@ -940,10 +895,10 @@ static int filter_screen(const PipeArgs& a, int64_t r0, int64_t seg, const float
 static int run_screen_spec(const PipeArgs& a, const WsLayout& L, char* ws, float* fv,
                            int64_t* fi, void* timer, hipStream_t st) {
   int rc;
-  const int64_t B = a.B, B_pad = a.B_pad, n_rows = a.n_rows;
+  const QueryOps& q = a.q;
+  const CatOps& c = a.c;
+  const int64_t B = q.B, B_pad = q.B_pad, n_rows = c.n_rows;
   const int32_t k = a.k, kprime = a.kprime;
-  uint64_t* cand = (uint64_t*)(ws + L.off_cand);
-  uint8_t* counts = (uint8_t*)(ws + L.off_counts);
   float* thr = (float*)(ws + L.off_thr);
   int* ovf = (int*)(ws + L.off_ovf);
   float* pooled = (float*)(ws + L.off_s);
@@ -961,10 +916,14 @@ static int run_screen_spec(const PipeArgs& a, const WsLayout& L, char* ws, float
   while (slots < EBT_FILTER_SLOTS_MAX &&
          (slots < 4.0 * per_group + 4.0 || n_cells * poisson_tail(1.5 * per_group, slots) > 1e-3))
     slots *= 2;
+  const HitSlots h{(uint64_t*)(ws + L.off_cand), L.ld_cand, slots, (uint8_t*)(ws + L.off_counts),
+                   L.ld_counts};
   // the lead tiles (the sample's first tiles, their scores kept by the pool GEMM): their hits
   // at theta_spec go into the first segment's first groups, taken by the same launch that finds
   // theta_spec (pool_kth); the filter then starts after them
-  const int64_t lead = given ? a.lead : L.spec_lead;
+  float* own_lead = (float*)(ws + L.off_lead);
+  const LeadIn li = given ? a.lead : LeadIn{own_lead, L.ld_lead, L.spec_lead};
+  const int64_t lead = li.tiles;
   if (lead > 0 && (lead * slots > L.ld_cand || lead > L.ld_counts || L.group_rows != 256)) {
     set_error("run_screen_spec: the lead does not fit the hit slots");
     return EBT_EINVAL;
@@ -973,27 +932,24 @@ static int run_screen_spec(const PipeArgs& a, const WsLayout& L, char* ws, float
     // the threshold, the empty list (-inf / -1), no overflow yet: one launch
     // (+ the caller's lead hits at theta into the first groups' slots)
     if (a.gsamp)   // the threshold from the gathered samples, in the same launch
-      rc = pool_kth(a.gsamp, a.gs_G, B, B_pad, a.gs_G, a.gs_j, tspec, st, fv, fi, kprime, ovf,
-                    a.lead_s, a.ld_lead, (int)lead, cand, L.ld_cand, slots, counts, L.ld_counts,
-                    a.gs_gj, a.gs_rstride);
+      rc = pool_kth(a.gsamp, a.gs_G, B, B_pad, a.gs_G, a.gs_j, tspec, fv, fi, kprime, ovf, li, h,
+                    a.gs, st);
     else
-      rc = spec_given_init(a.theta, B, B_pad, tspec, fv, fi, kprime, ovf, st, a.lead_s,
-                           a.ld_lead, (int)lead, cand, L.ld_cand, slots, counts, L.ld_counts);
+      rc = spec_given_init(a.theta, B, B_pad, tspec, fv, fi, kprime, ovf, li, h, st);
     if (rc) return rc;
   } else {
     {
       StageScope s(timer, EBT_STAGE_GEMM, st);
-      rc = screen_gemm_pool(a.qimg, B_pad, a.cimg, m, a.d_pad, a.ld_img, a.img_dtype, a.qscale,
-                            a.cscale, 256 * L.spec_stride, pooled, L.ld_s, st, lead,
-                            (float*)(ws + L.off_lead), L.ld_lead);
+      rc = screen_gemm_pool(q.qimg, B_pad, c.cimg, m, c.d_pad, c.ld_img, c.img_dtype, q.qscale,
+                            c.cscale, 256 * L.spec_stride, pooled, L.ld_s, st, lead, own_lead,
+                            L.ld_lead);
     }
     if (rc) return rc;
     {
       StageScope s(timer, EBT_STAGE_SELECT, st);
       // theta_spec, the empty list (-inf / -1) with no overflow yet, the lead's hits
-      rc = pool_kth(pooled, L.ld_s, B, B_pad, (int)(m / 64), L.spec_j, tspec, st, fv, fi, kprime,
-                    ovf, (const float*)(ws + L.off_lead), L.ld_lead, (int)lead, cand, L.ld_cand,
-                    slots, counts, L.ld_counts);
+      rc = pool_kth(pooled, L.ld_s, B, B_pad, (int)(m / 64), L.spec_j, tspec, fv, fi, kprime, ovf,
+                    li, h, {}, st);
     }
     if (rc) return rc;
   }
@@ -1059,13 +1015,12 @@ static int run_screen_spec(const PipeArgs& a, const WsLayout& L, char* ws, float
     const float* t = tspec;
     if (!first) {
       if (!thr_raised) {  // (the previous wave merge wrote it: no launch)
-        rc = spec_threshold(fv, kprime, B, B_pad, k, a.eps, tspec, thr, ovf, 0, st);
+        rc = spec_threshold(fv, kprime, B, B_pad, k, q.eps, tspec, thr, ovf, 0, st);
         if (rc) return rc;
       }
       t = thr;
     }
-    rc = filter_screen(a, r0, seg, t, cand + g0 * slots, L.ld_cand, slots, counts + g0,
-                       L.ld_counts, ovf, timer, st);
+    rc = filter_screen(a, r0, seg, t, from_group(h, g0), ovf, timer, st);
     if (rc) return rc;
     // the last wave merge also runs the final VERIFY of theta_spec (no separate launch)
     const bool fuse_verify = wave && !given && r0 + seg == n_rows;
@@ -1077,16 +1032,16 @@ static int run_screen_spec(const PipeArgs& a, const WsLayout& L, char* ws, float
     thr_raised = wave && !last;
     {
       StageScope s(timer, EBT_STAGE_MERGE_SELECT, st);
-      if (wave)
-        rc = merge_segment_wave(fv, fi, B, kprime, k, cand, L.ld_cand, slots, counts,
-                                L.ld_counts, groups, a.row_offset, a.excl_off, a.excl_rows, ovf,
-                                st, fuse_verify ? a.eps : nullptr, fuse_verify ? tspec : nullptr,
-                                last ? a.floor_out : nullptr, a.floor_w, a.eps,
-                                thr_raised ? thr : nullptr, tspec, a.eps, B_pad);
-      else  // sorted lists (the block merge sorts the union)
-        rc = merge_segment(fv, fi, B, kprime, cand, L.ld_cand, slots, counts, L.ld_counts,
-                           groups, a.row_offset, a.excl_off, a.excl_rows, ovf, st,
+      if (wave) {
+        WaveMergeOpts o{};
+        if (fuse_verify) o.verify = {tspec, q.eps};
+        if (last && a.floor_out) o.floor = {a.floor_out, a.floor_w, q.eps};
+        if (thr_raised) o.raise = {thr, tspec, q.eps, B_pad};
+        rc = merge_segment_wave(fv, fi, B, kprime, k, h, groups, c.row_offset, a.excl, ovf, st, o);
+      } else {  // sorted lists (the block merge sorts the union)
+        rc = merge_segment(fv, fi, B, kprime, h, groups, c.row_offset, a.excl, ovf, st,
                            rate * (double)(seg + g0 * L.group_rows));
+      }
     }
     if (rc) return rc;
     r0 += seg;
@@ -1095,7 +1050,7 @@ static int run_screen_spec(const PipeArgs& a, const WsLayout& L, char* ws, float
   // a caller's threshold is verified by the caller against the catalog-wide floor (the local
   // list may hold fewer than k rows: most of the global top k live on other shards)
   if (given || verified) return EBT_OK;
-  return spec_threshold(fv, kprime, B, B_pad, k, a.eps, tspec, nullptr, ovf, 1, st);
+  return spec_threshold(fv, kprime, B, B_pad, k, q.eps, tspec, nullptr, ovf, 1, st);
 }
 
 // The screen: the k' best approx candidates per query into fv/fi (LOCAL rows, sorted), by the
@@ -1103,12 +1058,13 @@ static int run_screen_spec(const PipeArgs& a, const WsLayout& L, char* ws, float
 static int run_screen(const PipeArgs& a, const WsLayout& L, char* ws, float* fv, int64_t* fi,
                       void* timer, hipStream_t st, ScreenOut* so) {
   int rc;
-  so->eps = a.eps;
+  const QueryOps& q = a.q;
+  const CatOps& c = a.c;
+  so->eps = q.eps;
   so->ovf = nullptr;
-  const int64_t B = a.B, B_pad = a.B_pad, n_rows = a.n_rows, row_offset = a.row_offset;
-  const int32_t k = a.k, kprime = a.kprime, d_pad = a.d_pad, ld_img = a.ld_img;
+  const int64_t B = q.B, B_pad = q.B_pad, n_rows = c.n_rows, row_offset = c.row_offset;
+  const int32_t k = a.k, kprime = a.kprime;
   if (a.flags & EBT_FLAG_EXACT) {  // float64 screen; its bound replaces the caller's eps
-    const ExactScreen ex{a.q64, a.d, a.cat, a.dtype, a.ld, a.gnorm64};
     float* xeps = (float*)(ws + L.off_eps);
     const float e = EBT_EXACT_EPS;
     uint32_t bits;
@@ -1117,16 +1073,9 @@ static int run_screen(const PipeArgs& a, const WsLayout& L, char* ws, float* fv,
                    "hipMemsetD32Async");
     if (rc) return rc;
     so->eps = xeps;
-    return head_topk(L, ws, nullptr, nullptr, B, B_pad, nullptr, nullptr, a.img_dtype, ld_img, 0,
-                     n_rows, d_pad, row_offset, a.excl_off, a.excl_rows, kprime, fv, fi, kprime,
-                     timer, st, &ex, a.allow);
+    return head_topk(a, L, ws, 0, n_rows, fv, fi, kprime, timer, st);
   }
-  if (!L.fused)
-    return head_topk(L, ws, a.qimg, a.qscale, B, B_pad, a.cimg, a.cscale, a.img_dtype, ld_img, 0,
-                     n_rows, d_pad, row_offset, a.excl_off, a.excl_rows, kprime, fv, fi, kprime,
-                     timer, st, nullptr, a.allow);
-  uint64_t* cand = (uint64_t*)(ws + L.off_cand);
-  uint8_t* counts = (uint8_t*)(ws + L.off_counts);
+  if (!L.fused) return head_topk(a, L, ws, 0, n_rows, fv, fi, kprime, timer, st);
   float* thr = (float*)(ws + L.off_thr);
   int* ovf = (int*)(ws + L.off_ovf);
   so->ovf = ovf;
@@ -1136,22 +1085,20 @@ static int run_screen(const PipeArgs& a, const WsLayout& L, char* ws, float* fv,
     float* S = (float*)(ws + L.off_s);
     {
       StageScope s(timer, EBT_STAGE_GEMM, st);
-      rc = screen_gemm(a.qimg, B_pad, a.cimg, L.head, d_pad, ld_img, a.img_dtype, a.qscale,
-                       a.cscale, S, L.ld_s, st);
+      rc = screen_gemm(q.qimg, B_pad, c.cimg, L.head, c.d_pad, c.ld_img, c.img_dtype, q.qscale,
+                       c.cscale, S, L.ld_s, st);
     }
     if (rc) return rc;
-    if (a.excl_off) {
+    if (a.excl.off) {
       StageScope s(timer, EBT_STAGE_MASK, st);
-      rc = mask_excluded(S, L.ld_s, B, row_offset, row_offset + L.head, a.excl_off, a.excl_rows,
+      rc = mask_excluded(S, L.ld_s, B, row_offset, row_offset + L.head, a.excl.off, a.excl.rows,
                          st);
       if (rc) return rc;
     }
     StageScope s(timer, EBT_STAGE_SELECT, st);
     rc = pilot_topk(S, L.ld_s, B, (int)L.head, 0, kprime, k, fv, fi, st);
   } else {
-    rc = head_topk(L, ws, a.qimg, a.qscale, B, B_pad, a.cimg, a.cscale, a.img_dtype, ld_img, 0,
-                   L.head, d_pad, row_offset, a.excl_off, a.excl_rows, kprime, fv, fi, kprime,
-                   timer, st);
+    rc = head_topk(a, L, ws, 0, L.head, fv, fi, kprime, timer, st);
   }
   if (rc) return rc;
   rc = hip_check(hipMemsetAsync(ovf, 0, (size_t)B_pad * 4, st), "hipMemsetAsync");
@@ -1181,19 +1128,17 @@ static int run_screen(const PipeArgs& a, const WsLayout& L, char* ws, float* fv,
     if (seg_cap > max_groups * L.group_rows) seg_cap = max_groups * L.group_rows;
     seg = seg < seg_cap ? seg : seg_cap;
     const int64_t groups = ceil_div(seg, L.group_rows);
-    rc = kth_threshold(fv, kprime, B, B_pad, k, a.eps, thr, st);
+    const HitSlots h{(uint64_t*)(ws + L.off_cand), L.ld_cand, slots,
+                     (uint8_t*)(ws + L.off_counts), L.ld_counts};
+    rc = kth_threshold(fv, kprime, B, B_pad, k, q.eps, thr, st);
     if (rc) return rc;
-    rc = filter_screen(a, r0, seg, thr, cand, L.ld_cand, slots, counts, L.ld_counts, ovf,
-                       timer, st);
+    rc = filter_screen(a, r0, seg, thr, h, ovf, timer, st);
     if (rc) return rc;
     {
       StageScope s(timer, EBT_STAGE_MERGE_SELECT, st);
-      rc = L.pilot ? merge_segment_wave(fv, fi, B, kprime, k, cand, L.ld_cand, slots, counts,
-                                        L.ld_counts, groups, row_offset, a.excl_off, a.excl_rows,
-                                        ovf, st)
-                   : merge_segment(fv, fi, B, kprime, cand, L.ld_cand, slots, counts,
-                                   L.ld_counts, groups, row_offset, a.excl_off, a.excl_rows, ovf,
-                                   st);
+      rc = L.pilot
+               ? merge_segment_wave(fv, fi, B, kprime, k, h, groups, row_offset, a.excl, ovf, st)
+               : merge_segment(fv, fi, B, kprime, h, groups, row_offset, a.excl, ovf, st);
     }
     if (rc) return rc;
     r0 += seg;
@@ -1201,73 +1146,109 @@ static int run_screen(const PipeArgs& a, const WsLayout& L, char* ws, float* fv,
   return EBT_OK;
 }
 
-}  // namespace ebt
-
-extern "C" {
-
-// ebt_cosine_topk_prepared, and with per-query allow masks ebt_cosine_topk_prepared_allowed:
-// allow != NULL runs the unfused screen (EBT_FLAG_NO_FUSE set here), its chunks masked twice
-static int cosine_topk_prepared_impl(
-    const char* who, const double* q64, const void* qimg, const float* qscale, const float* eps,
-    int64_t B, int64_t B_pad, const void* cat, int dtype, int64_t ld, const double* gnorm64,
-    const void* cimg, const float* cscale, int img_dtype, int32_t ld_img, int64_t n_rows,
-    int32_t d, int32_t d_pad, int64_t row_offset, const int64_t* excl_off,
-    const int64_t* excl_rows, int32_t k, int32_t kprime, int64_t chunk_rows, int flags,
-    void* workspace, size_t ws_bytes, double* out_scores, int64_t* out_rows, int32_t* certified,
-    void* timer, void* stream, const ebt_allow* allow) {
-  hipStream_t st = (hipStream_t)stream;
-  if (allow) flags |= EBT_FLAG_NO_FUSE;
-  PipeArgs a{q64, qimg, qscale, eps, B, B_pad, cat, dtype, ld, gnorm64, cimg, cscale,
-             img_dtype, ld_img, n_rows, d, d_pad, row_offset, excl_off, excl_rows, k, kprime,
-             chunk_rows, flags};
-  a.allow = allow;
+// The body every prepared or screen entry shares: the operand checks, the entry's own checks (in
+// its own words), the workspace layout and its size check, the screen into fv/fi (null: the
+// workspace's own list). The entry goes on with its tail.
+template <class OwnChecks>
+static int checked_screen(const PipeArgs& a, const char* who, OwnChecks own, void* workspace,
+                          size_t ws_bytes, float* fv, int64_t* fi, void* timer, hipStream_t st,
+                          ScreenOut* so) {
   int rc = check_pipe(a, who);
+  if (!rc) rc = own();
   if (rc) return rc;
-  if (!workspace || !out_scores || !out_rows || !certified) {
-    set_error("%s: null pointer", who);
-    return EBT_EINVAL;
-  }
-  if (allow) {
-    if (row_offset < 0) {
-      set_error("%s: row_offset=%lld < 0", who, (long long)row_offset);
-      return EBT_EINVAL;
-    }
-    rc = check_allow(allow, row_offset + n_rows, who);
-    if (rc) return rc;
-  }
-  const WsLayout L = ws_layout(B, B_pad, n_rows, kprime, chunk_rows, flags);
+  const WsLayout L = ws_layout(a.q.B, a.q.B_pad, a.c.n_rows, a.kprime, a.chunk_rows, a.flags);
   if (ws_bytes < L.bytes) {
     set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, L.bytes);
     return EBT_ENOMEM;
   }
   char* ws = (char*)workspace;
-  float* fv = (float*)(ws + L.off_fv);
-  int64_t* fi = (int64_t*)(ws + L.off_fi);
+  so->fv = fv ? fv : (float*)(ws + L.off_fv);
+  so->fi = fi ? fi : (int64_t*)(ws + L.off_fi);
+  so->theta = (const float*)(ws + L.off_tspec);
+  return run_screen(a, L, ws, so->fv, so->fi, timer, st, so);
+}
+
+// ebt_cosine_topk_prepared, and with per-query allow masks ebt_cosine_topk_prepared_allowed:
+// a.allow != NULL runs the unfused screen (EBT_FLAG_NO_FUSE set here), its chunks masked twice
+int topk_prepared(const PipeArgs& in, void* workspace, size_t ws_bytes, double* out_scores,
+                  int64_t* out_rows, int32_t* certified, void* timer, hipStream_t st) {
+  PipeArgs a = in;
+  if (a.allow) a.flags |= EBT_FLAG_NO_FUSE;
+  const char* who = a.allow ? "ebt_cosine_topk_prepared_allowed" : "ebt_cosine_topk_prepared";
+  const int64_t row_offset = a.c.row_offset;
   ScreenOut so{};
-  rc = run_screen(a, L, ws, fv, fi, timer, st, &so);
+  const int rc = checked_screen(a, who, [&]() -> int {
+    if (!workspace || !out_scores || !out_rows || !certified) {
+      set_error("%s: null pointer", who);
+      return EBT_EINVAL;
+    }
+    if (!a.allow) return EBT_OK;
+    if (row_offset < 0) {
+      set_error("%s: row_offset=%lld < 0", who, (long long)row_offset);
+      return EBT_EINVAL;
+    }
+    return check_allow(a.allow, row_offset + a.c.n_rows, who);
+  }, workspace, ws_bytes, nullptr, nullptr, timer, st, &so);
   if (rc) return rc;
   StageScope s(timer, EBT_STAGE_RESCORE, st);
   // (the rescore also checks each query's exclusion segment: certified = -3 when it is not
   // sorted ascending -- the check the C entry used to launch on its own, with a flag memset)
-  return rescore(q64, B, d, cat, dtype, ld, gnorm64, row_offset, fv, fi, kprime, k, n_rows,
-                 so.eps, nullptr, out_scores, out_rows, certified, st, so.ovf, 0,
-                 timer_rows(timer, st), 0, nullptr, excl_off, excl_rows);
+  return rescore(a.q.q64, a.q.B, a.c, {so.fv, so.fi, a.kprime, 0}, a.k, so.eps, nullptr,
+                 out_scores, out_rows, certified,
+                 {so.ovf, nullptr, a.excl, nullptr, timer_rows(timer, st)}, st);
 }
 
-int ebt_cosine_topk_prepared(const double* q64, const void* qimg, const float* qscale, const float* eps,
-                    int64_t B, int64_t B_pad, const void* cat, int dtype, int64_t ld,
-                    const double* gnorm64, const void* cimg, const float* cscale, int img_dtype,
-                    int32_t ld_img, int64_t n_rows, int32_t d, int32_t d_pad, int64_t row_offset,
-                    const int64_t* excl_off, const int64_t* excl_rows, int32_t k, int32_t kprime,
-                    int64_t chunk_rows, int flags, void* workspace, size_t ws_bytes,
-                    double* out_scores, int64_t* out_rows, int32_t* certified, void* timer,
-                    void* stream) {
-  return cosine_topk_prepared_impl("ebt_cosine_topk_prepared", q64, qimg, qscale, eps, B, B_pad,
-                                   cat, dtype, ld, gnorm64, cimg, cscale, img_dtype, ld_img,
-                                   n_rows, d, d_pad, row_offset, excl_off, excl_rows, k, kprime,
-                                   chunk_rows, flags, workspace, ws_bytes, out_scores, out_rows,
-                                   certified, timer, stream, nullptr);
+static int export_screen(const PipeArgs& a, const ScreenOut& so, int32_t* ovf_out, float* eps_out,
+                         hipStream_t st) {
+  return export_list(so.fi, a.q.B, a.kprime, a.c.row_offset, so.ovf, so.eps, ovf_out, eps_out, st);
 }
+int screen_export(const PipeArgs& a, void* workspace, size_t ws_bytes, float* list_vals,
+                  int64_t* list_rows, int32_t* ovf_out, float* eps_out, void* timer,
+                  hipStream_t st) {
+  ScreenOut so{};
+  const int rc = checked_screen(a, "ebt_cosine_screen", [&]() -> int {
+    if (!workspace || !list_vals || !list_rows || !ovf_out || !eps_out) {
+      set_error("ebt_cosine_screen: null pointer");
+      return EBT_EINVAL;
+    }
+    return EBT_OK;
+  }, workspace, ws_bytes, list_vals, list_rows, timer, st, &so);
+  return rc ? rc : export_screen(a, so, ovf_out, eps_out, st);
+}
+
+// The sharded step's screen at the shared threshold without ebt_cosine_screen_at_lead's export
+// launch: the list keeps LOCAL rows (the sharded rescore reads them with list base 0), and the
+// screen's thresholds, overflow flags and eps stay where the pipeline wrote them (*theta_dev,
+// *ovf_dev, *eps_dev point into the workspace / the prepared queries).
+int screen_at_local(const PipeArgs& in, void* workspace, size_t ws_bytes, float* list_vals,
+                    int64_t* list_rows, const float** theta_dev, const int** ovf_dev,
+                    const float** eps_dev, void* timer, hipStream_t st) {
+  PipeArgs a = in;
+  a.flags = EBT_FLAG_THETA;
+  const int64_t lead = a.lead.tiles;
+  ScreenOut so{};
+  const int rc = checked_screen(a, "screen_at_local", [&]() -> int {
+    if (!workspace || !list_vals || !list_rows || !a.gsamp || !theta_dev || !ovf_dev ||
+        !eps_dev || !merge_wave_fits(a.kprime) || !(a.hits >= 0.0) || lead < 0 || a.gs_G < 1 ||
+        a.gs_G > 2048 || (a.floor_out && (a.floor_w < 1 || a.floor_w > a.k)) || a.gs.gj < 1 ||
+        a.gs_G % a.gs.gj != 0 || a.gs.rstride < a.q.B * (int64_t)a.gs.gj || a.gs_j < 1 ||
+        (lead > 0 && (!a.lead.scores || a.lead.ld < 256 * lead || 256 * lead >= a.c.n_rows))) {
+      set_error("screen_at_local: bad arguments (kprime=%d, lead=%lld, G=%d, gj=%d, j=%d)",
+                a.kprime, (long long)lead, a.gs_G, a.gs.gj, a.gs_j);
+      return EBT_EINVAL;
+    }
+    return EBT_OK;
+  }, workspace, ws_bytes, list_vals, list_rows, timer, st, &so);
+  if (rc) return rc;
+  *ovf_dev = so.ovf;
+  *eps_dev = so.eps;
+  *theta_dev = so.theta;
+  return EBT_OK;
+}
+
+}  // namespace ebt
+
+extern "C" {
 
 int ebt_cosine_topk_prepared_allowed(
     const double* q64, const void* qimg, const float* qscale, const float* eps, int64_t B,
@@ -1277,13 +1258,29 @@ int ebt_cosine_topk_prepared_allowed(
     const int64_t* excl_rows, int32_t k, int32_t kprime, int64_t chunk_rows, int flags,
     void* workspace, size_t ws_bytes, double* out_scores, int64_t* out_rows, int32_t* certified,
     void* timer, void* stream, const ebt_allow* allow) {
-  return cosine_topk_prepared_impl(allow ? "ebt_cosine_topk_prepared_allowed"
-                                         : "ebt_cosine_topk_prepared",
-                                   q64, qimg, qscale, eps, B, B_pad, cat, dtype, ld, gnorm64,
-                                   cimg, cscale, img_dtype, ld_img, n_rows, d, d_pad, row_offset,
-                                   excl_off, excl_rows, k, kprime, chunk_rows, flags, workspace,
-                                   ws_bytes, out_scores, out_rows, certified, timer, stream,
-                                   allow);
+  PipeArgs a{{q64, qimg, qscale, eps, B, B_pad},
+             {cat, dtype, ld, gnorm64, cimg, cscale, img_dtype, ld_img, n_rows, d, d_pad,
+              row_offset},
+             {excl_off, excl_rows}, k, kprime, chunk_rows, flags};
+  a.allow = allow;
+  return topk_prepared(a, workspace, ws_bytes, out_scores, out_rows, certified, timer,
+                       (hipStream_t)stream);
+}
+
+// (= the allowed entry without masks, which then reports under this name)
+int ebt_cosine_topk_prepared(const double* q64, const void* qimg, const float* qscale, const float* eps,
+                    int64_t B, int64_t B_pad, const void* cat, int dtype, int64_t ld,
+                    const double* gnorm64, const void* cimg, const float* cscale, int img_dtype,
+                    int32_t ld_img, int64_t n_rows, int32_t d, int32_t d_pad, int64_t row_offset,
+                    const int64_t* excl_off, const int64_t* excl_rows, int32_t k, int32_t kprime,
+                    int64_t chunk_rows, int flags, void* workspace, size_t ws_bytes,
+                    double* out_scores, int64_t* out_rows, int32_t* certified, void* timer,
+                    void* stream) {
+  return ebt_cosine_topk_prepared_allowed(q64, qimg, qscale, eps, B, B_pad, cat, dtype, ld,
+                                          gnorm64, cimg, cscale, img_dtype, ld_img, n_rows, d,
+                                          d_pad, row_offset, excl_off, excl_rows, k, kprime,
+                                          chunk_rows, flags, workspace, ws_bytes, out_scores,
+                                          out_rows, certified, timer, stream, nullptr);
 }
 
 int ebt_cosine_screen(const double* q64, const void* qimg, const float* qscale, const float* eps,
@@ -1294,26 +1291,12 @@ int ebt_cosine_screen(const double* q64, const void* qimg, const float* qscale, 
                       int64_t chunk_rows, int flags, void* workspace, size_t ws_bytes,
                       float* list_vals, int64_t* list_rows, int32_t* ovf_out, float* eps_out,
                       void* timer, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const PipeArgs a{q64, qimg, qscale, eps, B, B_pad, cat, dtype, ld, gnorm64, cimg, cscale,
-                   img_dtype, ld_img, n_rows, d, d_pad, row_offset, excl_off, excl_rows, k, kprime,
-                   chunk_rows, flags};
-  int rc = check_pipe(a, "ebt_cosine_screen");
-  if (rc) return rc;
-  if (!workspace || !list_vals || !list_rows || !ovf_out || !eps_out) {
-    set_error("ebt_cosine_screen: null pointer");
-    return EBT_EINVAL;
-  }
-  const WsLayout L = ws_layout(B, B_pad, n_rows, kprime, chunk_rows, flags);
-  if (ws_bytes < L.bytes) {
-    set_error("ebt_cosine_screen: workspace %zu < %zu bytes", ws_bytes, L.bytes);
-    return EBT_ENOMEM;
-  }
-  char* ws = (char*)workspace;
-  ScreenOut so{};
-  rc = run_screen(a, L, ws, list_vals, list_rows, timer, st, &so);
-  if (rc) return rc;
-  return export_list(list_rows, B, kprime, row_offset, so.ovf, so.eps, ovf_out, eps_out, st);
+  const PipeArgs a{{q64, qimg, qscale, eps, B, B_pad},
+                   {cat, dtype, ld, gnorm64, cimg, cscale, img_dtype, ld_img, n_rows, d, d_pad,
+                    row_offset},
+                   {excl_off, excl_rows}, k, kprime, chunk_rows, flags};
+  return screen_export(a, workspace, ws_bytes, list_vals, list_rows, ovf_out, eps_out, timer,
+                       (hipStream_t)stream);
 }
 
 int ebt_cosine_screen_at(const double* q64, const void* qimg, const float* qscale,
@@ -1332,6 +1315,7 @@ int ebt_cosine_screen_at(const double* q64, const void* qimg, const float* qscal
                                    0, nullptr, 0, timer, stream);
 }
 
+// (reports as ebt_cosine_screen_at, which is this entry without a lead, but for the lead's check)
 int ebt_cosine_screen_at_lead(const double* q64, const void* qimg, const float* qscale,
                               const float* eps, int64_t B, int64_t B_pad, const void* cat,
                               int dtype, int64_t ld, const double* gnorm64, const void* cimg,
@@ -1345,103 +1329,35 @@ int ebt_cosine_screen_at_lead(const double* q64, const void* qimg, const float* 
                               void* timer, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   flags |= EBT_FLAG_THETA;
-  PipeArgs a{q64, qimg, qscale, eps, B, B_pad, cat, dtype, ld, gnorm64, cimg, cscale,
-             img_dtype, ld_img, n_rows, d, d_pad, row_offset, excl_off, excl_rows, k, kprime,
-             chunk_rows, flags};
+  PipeArgs a{{q64, qimg, qscale, eps, B, B_pad},
+             {cat, dtype, ld, gnorm64, cimg, cscale, img_dtype, ld_img, n_rows, d, d_pad,
+              row_offset},
+             {excl_off, excl_rows}, k, kprime, chunk_rows, flags};
   a.theta = theta;
   a.hits = hits;
-  a.lead = lead;
-  a.lead_s = lead_scores;
-  a.ld_lead = ld_lead;
-  int rc = check_pipe(a, "ebt_cosine_screen_at");
-  if (rc) return rc;
-  if (lead < 0 || (lead > 0 && (!lead_scores || ld_lead < 256 * lead || 256 * lead >= n_rows))) {
-    set_error("ebt_cosine_screen_at_lead: bad lead (lead=%lld, ld_lead=%lld, n_rows=%lld)",
-              (long long)lead, (long long)ld_lead, (long long)n_rows);
-    return EBT_EINVAL;
-  }
-  if (!workspace || !list_vals || !list_rows || !ovf_out || !eps_out || !theta) {
-    set_error("ebt_cosine_screen_at: null pointer");
-    return EBT_EINVAL;
-  }
-  if ((flags & (EBT_FLAG_NO_FUSE | EBT_FLAG_EXACT)) || !merge_wave_fits(kprime) ||
-      !(hits >= 0.0)) {
-    set_error("ebt_cosine_screen_at: needs the fused screen with kprime <= 512 (kprime=%d, "
-              "flags=%d, hits=%g)", kprime, flags, hits);
-    return EBT_EINVAL;
-  }
-  const WsLayout L = ws_layout(B, B_pad, n_rows, kprime, chunk_rows, flags);
-  if (ws_bytes < L.bytes) {
-    set_error("ebt_cosine_screen_at: workspace %zu < %zu bytes", ws_bytes, L.bytes);
-    return EBT_ENOMEM;
-  }
-  char* ws = (char*)workspace;
+  a.lead = {lead_scores, ld_lead, lead};
   ScreenOut so{};
-  rc = run_screen(a, L, ws, list_vals, list_rows, timer, st, &so);
-  if (rc) return rc;
-  return export_list(list_rows, B, kprime, row_offset, so.ovf, so.eps, ovf_out, eps_out, st);
+  const int rc = checked_screen(a, "ebt_cosine_screen_at", [&]() -> int {
+    if (lead < 0 ||
+        (lead > 0 && (!lead_scores || ld_lead < 256 * lead || 256 * lead >= n_rows))) {
+      set_error("ebt_cosine_screen_at_lead: bad lead (lead=%lld, ld_lead=%lld, n_rows=%lld)",
+                (long long)lead, (long long)ld_lead, (long long)n_rows);
+      return EBT_EINVAL;
+    }
+    if (!workspace || !list_vals || !list_rows || !ovf_out || !eps_out || !theta) {
+      set_error("ebt_cosine_screen_at: null pointer");
+      return EBT_EINVAL;
+    }
+    if ((flags & (EBT_FLAG_NO_FUSE | EBT_FLAG_EXACT)) || !merge_wave_fits(kprime) ||
+        !(hits >= 0.0)) {
+      set_error("ebt_cosine_screen_at: needs the fused screen with kprime <= 512 (kprime=%d, "
+                "flags=%d, hits=%g)", kprime, flags, hits);
+      return EBT_EINVAL;
+    }
+    return EBT_OK;
+  }, workspace, ws_bytes, list_vals, list_rows, timer, st, &so);
+  return rc ? rc : export_screen(a, so, ovf_out, eps_out, st);
 }
-
-}  // extern "C"
-
-namespace ebt {
-// The sharded step's screen at the shared threshold without ebt_cosine_screen_at_lead's export
-// launch (sharded.hip): the list keeps LOCAL rows (the sharded rescore reads them with list base
-// 0), and the screen's own overflow flags and eps stay where the pipeline wrote them (*ovf_dev,
-// *eps_dev point into the workspace / the prepared queries).
-int screen_at_local(const double* q64, const void* qimg, const float* qscale, const float* eps,
-                    int64_t B, int64_t B_pad, const void* cat, int dtype, int64_t ld,
-                    const double* gnorm64, const void* cimg, const float* cscale, int img_dtype,
-                    int32_t ld_img, int64_t n_rows, int32_t d, int32_t d_pad, int64_t row_offset,
-                    const int64_t* excl_off, const int64_t* excl_rows, int32_t k, int32_t kprime,
-                    int64_t chunk_rows, void* workspace, size_t ws_bytes, float* list_vals,
-                    int64_t* list_rows, const float* gsamp, int64_t gs_rstride, int gs_G,
-                    int gs_gj, int gs_j, double hits, int64_t lead, const float* lead_scores,
-                    int64_t ld_lead, const float** theta_dev, const int** ovf_dev,
-                    const float** eps_dev, void* timer, hipStream_t st, float* floor_out,
-                    int floor_w) {
-  const int flags = EBT_FLAG_THETA;
-  PipeArgs a{q64, qimg, qscale, eps, B, B_pad, cat, dtype, ld, gnorm64, cimg, cscale,
-             img_dtype, ld_img, n_rows, d, d_pad, row_offset, excl_off, excl_rows, k, kprime,
-             chunk_rows, flags};
-  a.hits = hits;
-  a.lead = lead;
-  a.lead_s = lead_scores;
-  a.ld_lead = ld_lead;
-  a.gsamp = gsamp;
-  a.gs_rstride = gs_rstride;
-  a.gs_G = gs_G;
-  a.gs_gj = gs_gj;
-  a.gs_j = gs_j;
-  a.floor_out = floor_out;
-  a.floor_w = floor_w;
-  int rc = check_pipe(a, "screen_at_local");
-  if (rc) return rc;
-  if (!workspace || !list_vals || !list_rows || !gsamp || !theta_dev || !ovf_dev || !eps_dev ||
-      !merge_wave_fits(kprime) || !(hits >= 0.0) || lead < 0 || gs_G < 1 || gs_G > 2048 ||
-      (floor_out && (floor_w < 1 || floor_w > k)) ||
-      gs_gj < 1 || gs_G % gs_gj != 0 || gs_rstride < B * (int64_t)gs_gj || gs_j < 1 ||
-      (lead > 0 && (!lead_scores || ld_lead < 256 * lead || 256 * lead >= n_rows))) {
-    set_error("screen_at_local: bad arguments (kprime=%d, lead=%lld, G=%d, gj=%d, j=%d)", kprime,
-              (long long)lead, gs_G, gs_gj, gs_j);
-    return EBT_EINVAL;
-  }
-  const WsLayout L = ws_layout(B, B_pad, n_rows, kprime, chunk_rows, flags);
-  if (ws_bytes < L.bytes) {
-    set_error("screen_at_local: workspace %zu < %zu bytes", ws_bytes, L.bytes);
-    return EBT_ENOMEM;
-  }
-  ScreenOut so{};
-  rc = run_screen(a, L, (char*)workspace, list_vals, list_rows, timer, st, &so);
-  if (rc) return rc;
-  *ovf_dev = so.ovf;
-  *eps_dev = so.eps;
-  *theta_dev = (const float*)((char*)workspace + L.off_tspec);
-  return EBT_OK;
-}
-}  // namespace ebt
-
-extern "C" {
 
 int ebt_cosine_sample(const void* qimg, const float* qscale, int64_t B_pad, const void* cimg,
                       const float* cscale, int img_dtype, int32_t ld_img, int64_t n_rows,
@@ -1474,7 +1390,8 @@ int ebt_cosine_sample_lead(const void* qimg, const float* qscale, int64_t B_pad,
 
 int ebt_pool_kth(const float* pooled, int64_t ld, int64_t B, int64_t B_pad, int32_t G, int32_t j,
                  float* theta, void* stream) {
-  return pool_kth(pooled, ld, B, B_pad, G, j, theta, (hipStream_t)stream);
+  return pool_kth(pooled, ld, B, B_pad, G, j, theta, nullptr, nullptr, 0, nullptr, {}, {}, {},
+                  (hipStream_t)stream);  // (no list to start, no lead)
 }
 
 int ebt_rescore_owned(const double* q64, int64_t B, int32_t d, const void* cat, int dtype,

@@ -401,14 +401,15 @@ int run_prepared(const ebt_catalog& c, const PrepLayout& P, char* base, int64_t 
                  int64_t chunk, int flags, char* pass, size_t pass_bytes, double* out_s,
                  int64_t* out_r, int32_t* cert, void* timer, hipStream_t st,
                  const ebt_allow* allow) {
-  const bool exact = flags & EBT_FLAG_EXACT;
-  return ebt_cosine_topk_prepared_allowed(
-      (const double*)(base + P.q64), exact ? nullptr : base + P.qimg,
-      exact ? nullptr : (const float*)(base + P.qscale),
-      exact ? nullptr : (const float*)(base + P.eps), B, pad_batch(B), c.data, c.dtype, c.ld,
-      c.gnorm64, c.image, c.cscale, c.img_dtype, c.ld_img, c.n, c.d, c.d_pad, c.row_offset,
-      excl_off, excl_rows, k_eff, kp, chunk, flags, pass, pass_bytes, out_s, out_r, cert, timer,
-      st, allow);
+  QueryOps q{(const double*)(base + P.q64), nullptr, nullptr, nullptr, B, pad_batch(B)};
+  if (!(flags & EBT_FLAG_EXACT)) {  // (the float64 screen takes no image of the queries)
+    q.qimg = base + P.qimg;
+    q.qscale = (const float*)(base + P.qscale);
+    q.eps = (const float*)(base + P.eps);
+  }
+  PipeArgs a{q, cat_ops(c), {excl_off, excl_rows}, k_eff, kp, chunk, flags};
+  a.allow = allow;
+  return topk_prepared(a, pass, pass_bytes, out_s, out_r, cert, timer, st);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
-// Every ebt:: function that one .hip file of libebert defines and another calls, declared once.
-// Included after common.h by the defining file and by every calling file, so that a changed
-// signature fails to compile instead of failing when the library is loaded. Default arguments
-// live here only.
+// Every ebt:: function that one .hip file of libebert defines and another calls, declared once,
+// and the operand records those functions take. Included after common.h by the defining file and
+// by every calling file, so that a changed signature fails to compile instead of failing when the
+// library is loaded. Default arguments live here only, and a declaration has at most one: what is
+// optional beyond that is a named record whose empty value ({}) switches it off.
 //
 // Linkage rule of csrc/ (the .hip files are linked into one library):
 //   * A type or function used by one .hip file only is file-local: in an anonymous namespace, or
@@ -9,8 +10,10 @@
 //   * Exception: a type named in a __global__ signature (EpiArgs, QpArgs, LeadArgs, UpdArgs,
 //     MoveArgs, GatherArgs, ExclArgs, DenseSrc, PackedSrc) or used in device code keeps its name
 //     and linkage, so that kernel symbols do not change; its name is unique in the library.
-//   * A type shared by two files is defined in exactly one header (common.h, driver.h) under a
-//     name that no .hip file defines.
+//   * A type shared by two files is defined in exactly one header (common.h, here, driver.h) under
+//     a name that no .hip file defines. Here: the operand records QueryOps, CatOps, ExclCsr,
+//     HitSlots, LeadIn, GatheredSamples, PipeArgs, WaveMergeOpts, CandList, RescoreExtras --
+//     host-only aggregates, filled by name at the one place where positional arguments come in.
 //   * A function with external linkage is declared in common.h, here, or in driver.h.
 #pragma once
 
@@ -18,27 +21,99 @@
 
 namespace ebt {
 
+// ---- operand records -------------------------------------------------------------------------
+// The prepared queries (the ebt_query_* outputs)
+struct QueryOps {
+  const double* q64;
+  const void* qimg;
+  const float *qscale, *eps;
+  int64_t B, B_pad;
+};
+// A (shard of a) catalog, in the order of the C entries' arguments
+struct CatOps {
+  const void* cat; int dtype; int64_t ld; const double* gnorm64;          // rows, float64 norms
+  const void* cimg; const float* cscale; int img_dtype; int32_t ld_img;   // 16-bit image, scales
+  int64_t n_rows; int32_t d, d_pad; int64_t row_offset;
+};
+inline CatOps cat_ops(const ebt_catalog& c) {
+  return {c.data, c.dtype, c.ld, c.gnorm64, c.image, c.cscale, c.img_dtype, c.ld_img, c.n, c.d,
+          c.d_pad, c.row_offset};
+}
+// Per-query excluded rows as a CSR (both null: none)
+struct ExclCsr { const int64_t *off, *rows; };
+// The filter GEMM's per-group hit slots: group g of query b holds counts[b * ld_counts + g] hits
+// at cand[b * ld_cand + g * slots ...]; from_group: the same slots seen from group g on
+struct HitSlots {
+  uint64_t* cand; int64_t ld_cand; int slots;
+  uint8_t* counts; int64_t ld_counts;
+};
+inline HitSlots from_group(HitSlots h, int64_t g) {
+  return {h.cand + g * h.slots, h.ld_cand, h.slots, h.counts + g, h.ld_counts};
+}
+// A sample lead: the stored scores [B_pad][ld] of the catalog's first `tiles` 256-row tiles
+struct LeadIn { const float* scores; int64_t ld, tiles; };
+// The all-gathered sample maxima of a row-sharded catalog, read in place: [R][B][gj], ranks
+// rstride floats apart (gj = 0: a plain [B][ld] row per query)
+struct GatheredSamples { int gj; int64_t rstride; };
+
+// One run of the prepared pipeline: the operands plus what its entry switches on
+struct PipeArgs {
+  QueryOps q;
+  CatOps c;
+  ExclCsr excl;
+  int32_t k, kprime; int64_t chunk_rows; int flags;
+  // ebt_cosine_screen_at: the caller's per-query threshold [B] and expected hits per query
+  const float* theta = nullptr; double hits = 0.0;
+  // ebt_cosine_screen_at_lead: the caller's lead, its scores stored by ebt_cosine_sample_lead
+  LeadIn lead = {};
+  // screen_at_local: instead of theta, the threshold as the gs_j-th of the all-gathered sample
+  // maxima (gs_G per query), taken by the launch that starts the list and takes the lead's hits
+  const float* gsamp = nullptr; GatheredSamples gs = {}; int gs_G = 0, gs_j = 0;
+  // screen_at_local: the row-sharded step's floor entries ([B][floor_w + 1], ebt_floor_pack's
+  // layout) written by the screen's last wave merge
+  float* floor_out = nullptr; int floor_w = 0;
+  // ebt_cosine_topk_prepared_allowed: the per-query allow masks (unfused and float64 screens
+  // only: the entry sets EBT_FLAG_NO_FUSE), null = unfiltered
+  const ebt_allow* allow = nullptr;
+};
+
+// What the wave merge does on top of merging, each group off when its first pointer is null: the
+// VERIFY of theta_spec on the final list; the row-sharded step's floor entries [B][width + 1];
+// the next segment's threshold [B_pad] = max(in, the k-th - 2 eps)
+struct WaveMergeOpts {
+  struct { const float *theta_spec, *eps; } verify;
+  struct { float* out; int width; const float* eps; } floor;
+  struct { float* out; const float *in, *eps; int64_t B_pad; } raise;
+};
+
+// A candidate list per query: [B][kprime] approx scores and rows; the rescore reads list row r as
+// local row r - list_base (0: a list of LOCAL rows; the shard's row_offset: of GLOBAL rows)
+struct CandList { const float* vals; const int64_t* rows; int32_t kprime; int64_t list_base; };
+// What a rescore takes beyond the list, each null = off: the fused screen's overflow flags, the
+// caller's threshold, the exclusion CSR (order check), the pack count, the timer's row counters
+struct RescoreExtras {
+  const int* ovf; const float* theta; ExclCsr excl;
+  const ShardPackOut* pack; unsigned long long* gathered;
+};
+
 // ---- api.hip ---------------------------------------------------------------------------------
 int64_t shard_lead_room(int64_t B_pad, int64_t n_rows, int64_t sample_tiles);
 int64_t shard_lead_tiles(int64_t B_pad, int64_t n_rows, int64_t sample_tiles);
-int rescore_sharded(const double* q64, int64_t B, int32_t d, const void* cat, int dtype,
-                    int64_t ld, const double* gnorm64, int64_t row_offset, const float* cand_vals,
-                    const int64_t* cand_rows, int32_t kprime, int32_t k, int64_t n_rows,
+// x.gathered is taken from the timer
+int rescore_sharded(const double* q64, int64_t B, const CatOps& c, const CandList& l, int32_t k,
                     const float* eps, const double* t_floor, double* out_s, int64_t* out_r,
-                    int32_t* certified, const int* ovf, const float* theta, void* timer,
-                    hipStream_t st, int64_t list_base, const int64_t* excl_off,
-                    const int64_t* excl_rows, const ShardPackOut* pack);
-int screen_at_local(const double* q64, const void* qimg, const float* qscale, const float* eps,
-                    int64_t B, int64_t B_pad, const void* cat, int dtype, int64_t ld,
-                    const double* gnorm64, const void* cimg, const float* cscale, int img_dtype,
-                    int32_t ld_img, int64_t n_rows, int32_t d, int32_t d_pad, int64_t row_offset,
-                    const int64_t* excl_off, const int64_t* excl_rows, int32_t k, int32_t kprime,
-                    int64_t chunk_rows, void* workspace, size_t ws_bytes, float* list_vals,
-                    int64_t* list_rows, const float* gsamp, int64_t gs_rstride, int gs_G,
-                    int gs_gj, int gs_j, double hits, int64_t lead, const float* lead_scores,
-                    int64_t ld_lead, const float** theta_dev, const int** ovf_dev,
-                    const float** eps_dev, void* timer, hipStream_t st, float* floor_out,
-                    int floor_w);
+                    int32_t* certified, RescoreExtras x, void* timer, hipStream_t st);
+// ebt_cosine_topk_prepared (a.allow == null) / ebt_cosine_topk_prepared_allowed
+int topk_prepared(const PipeArgs& a, void* workspace, size_t ws_bytes, double* out_scores,
+                  int64_t* out_rows, int32_t* certified, void* timer, hipStream_t st);
+// ebt_cosine_screen
+int screen_export(const PipeArgs& a, void* workspace, size_t ws_bytes, float* list_vals,
+                  int64_t* list_rows, int32_t* ovf_out, float* eps_out, void* timer,
+                  hipStream_t st);
+// the screen at the threshold taken from a.gsamp (flags = EBT_FLAG_THETA, whatever a.flags says)
+int screen_at_local(const PipeArgs& a, void* workspace, size_t ws_bytes, float* list_vals,
+                    int64_t* list_rows, const float** theta_dev, const int** ovf_dev,
+                    const float** eps_dev, void* timer, hipStream_t st);
 
 // ---- screen_gemm.hip -------------------------------------------------------------------------
 int64_t gemm_cus();
@@ -48,8 +123,7 @@ int screen_gemm(const void* qimg, int64_t B_pad, const void* cimg, int64_t n_row
 int screen_gemm_pool(const void* qimg, int64_t B_pad, const void* cimg, int64_t n_rows,
                      int32_t d_pad, int32_t ld_img, int img_dtype, const float* qscale,
                      const float* cscale, int64_t cstride, float* pooled, int64_t ld_pooled,
-                     hipStream_t stream, int64_t lead = 0, float* lead_scores = nullptr,
-                     int64_t ld_lead = 0);
+                     hipStream_t stream, int64_t lead, float* lead_scores, int64_t ld_lead);
 int64_t filter_group_rows(int64_t B_pad);
 int screen_gemm_filter(const void* qimg, int64_t B_pad, const void* cimg, int64_t n_rows,
                        int32_t d_pad, int32_t ld_img, int img_dtype, const float* qscale,
@@ -62,36 +136,30 @@ int64_t filter_split_rows(int64_t B_pad, int64_t n_rows);
 int select_topk(const float* vals, const int64_t* idx, int64_t ld, int64_t B, int64_t n,
                 int64_t idx_base, int32_t kprime, int32_t segs, float* out_vals, int64_t* out_idx,
                 int64_t ld_out, hipStream_t stream);
-int merge_segment(float* fv, int64_t* fi, int64_t B, int kprime, const uint64_t* cand,
-                  int64_t ld_cand, int slots, const uint8_t* counts, int64_t ld_counts,
-                  int64_t n_groups, int64_t row_offset, const int64_t* eo, const int64_t* er,
-                  int* ovf, hipStream_t st, double expect_hits = 0.0);
+int merge_segment(float* fv, int64_t* fi, int64_t B, int kprime, const HitSlots& h,
+                  int64_t n_groups, int64_t row_offset, const ExclCsr& excl, int* ovf,
+                  hipStream_t st, double expect_hits = 0.0);
 bool merge_wave_fits(int kprime);
 int merge_block_capacity(int kprime);
 int64_t merge_block_max_groups(int kprime);
 int64_t merge_wave_max_groups();
 int merge_wave_capacity();
-int merge_segment_wave(float* fv, int64_t* fi, int64_t B, int kprime, int k, const uint64_t* cand,
-                       int64_t ld_cand, int slots, const uint8_t* counts, int64_t ld_counts,
-                       int64_t n_groups, int64_t row_offset, const int64_t* eo, const int64_t* er,
-                       int* ovf, hipStream_t st, const float* veps = nullptr,
-                       const float* vspec = nullptr, float* fout = nullptr, int fw = 0,
-                       const float* feps = nullptr, float* tout = nullptr,
-                       const float* tin = nullptr, const float* teps = nullptr, int64_t B_pad = 0);
+int merge_segment_wave(float* fv, int64_t* fi, int64_t B, int kprime, int k, const HitSlots& h,
+                       int64_t n_groups, int64_t row_offset, const ExclCsr& excl, int* ovf,
+                       hipStream_t st, const WaveMergeOpts& o = {});
 int pilot_topk(const float* S, int64_t ld_s, int64_t B, int n, int64_t idx_base, int kprime, int k,
                float* fv, int64_t* fi, hipStream_t st);
 int kth_threshold(const float* vals, int64_t ld, int64_t B, int64_t B_pad, int k, const float* eps,
                   float* thr, hipStream_t st);
+// thr[b] = the j-th largest of query b's G pooled maxima; with fv the launch also starts the
+// empty list fv/fi (k' entries, ovf 0), and with lead.tiles > 0 takes the lead's hits at the
+// threshold into h's first groups
 int pool_kth(const float* pool, int64_t ld, int64_t B, int64_t B_pad, int G, int j, float* thr,
-             hipStream_t st, float* fv = nullptr, int64_t* fi = nullptr, int kprime = 0,
-             int* ovf = nullptr, const float* lead_s = nullptr, int64_t ld_lead = 0, int lead = 0,
-             uint64_t* cand = nullptr, int64_t ld_cand = 0, int slots = 0,
-             uint8_t* counts = nullptr, int64_t ld_counts = 0, int gj = 0, int64_t rstride = 0);
+             float* fv, int64_t* fi, int kprime, int* ovf, const LeadIn& lead, const HitSlots& h,
+             const GatheredSamples& gs, hipStream_t st);
 int spec_given_init(const float* theta, int64_t B, int64_t B_pad, float* tspec, float* fv,
-                    int64_t* fi, int kprime, int* ovf, hipStream_t st,
-                    const float* lead_s = nullptr, int64_t ld_lead = 0, int lead = 0,
-                    uint64_t* cand = nullptr, int64_t ld_cand = 0, int slots = 0,
-                    uint8_t* counts = nullptr, int64_t ld_counts = 0);
+                    int64_t* fi, int kprime, int* ovf, const LeadIn& lead, const HitSlots& h,
+                    hipStream_t st);
 int spec_threshold(const float* vals, int64_t ld, int64_t B, int64_t B_pad, int k,
                    const float* eps, const float* thr_spec, float* thr, int* ovf, int mode,
                    hipStream_t st);
@@ -106,11 +174,11 @@ int query_dense(const void* q, int dtype, int64_t B, int32_t d, int64_t ldq, dou
                 hipStream_t st);
 int query_liked_sum(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm,
                     int64_t B, const int64_t* off, const int64_t* rows, double* q64,
-                    hipStream_t st, int64_t row_offset = 0, int64_t n_local = 0);
+                    hipStream_t st, int64_t row_offset, int64_t n_local);
 // the weighted sum sum_l w_l x_l / g_l (wts parallel to rows), and q64[b] *= 1 / sum_l |w_l|
 int query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm,
                      int64_t B, const int64_t* off, const int64_t* rows, const double* wts,
-                     double* q64, hipStream_t st, int64_t row_offset = 0, int64_t n_local = 0);
+                     double* q64, hipStream_t st, int64_t row_offset, int64_t n_local);
 int scale_by_abs_weight_sum(double* q64, int64_t B, int32_t d, const int64_t* off,
                             const double* wts, hipStream_t st);
 int scale_rows_f64(double* q64, int64_t B, int32_t d, const double* scale, hipStream_t st);
@@ -129,13 +197,10 @@ int mask_allowed(float* s, int64_t ld, int64_t B, int64_t c0, int64_t c1, const 
                  hipStream_t st);
 
 // ---- rescore.hip -----------------------------------------------------------------------------
-int rescore(const double* q64, int64_t B, int32_t d, const void* cat, int dtype, int64_t ld,
-            const double* gnorm, int64_t row_offset, const float* cand_vals,
-            const int64_t* cand_rows, int32_t kprime, int32_t k, int64_t n_rows, const float* eps,
-            const double* t_floor, double* out_s, int64_t* out_r, int32_t* certified,
-            hipStream_t st, const int* ovf_cnt, int ovf_cap, unsigned long long* gathered,
-            int64_t list_base = 0, const float* theta = nullptr, const int64_t* excl_off = nullptr,
-            const int64_t* excl_rows = nullptr, const ShardPackOut* pack = nullptr);
+// (of c: the rows, their norms, n_rows, d and row_offset; the screening image is not read)
+int rescore(const double* q64, int64_t B, const CatOps& c, const CandList& l, int32_t k,
+            const float* eps, const double* t_floor, double* out_s, int64_t* out_r,
+            int32_t* certified, const RescoreExtras& x, hipStream_t st);
 int merge_topk(const double* scores, const int64_t* rows, int32_t R, int64_t B, int32_t k,
                double* out_s, int64_t* out_r, hipStream_t st);
 int shard_pack_lens(const double* scores, const int64_t* rows, int64_t B, int32_t k, int64_t cap,

@@ -789,13 +789,18 @@ static size_t rescore_lds_bytes(int d, int kprime) {
   return 8 * (size_t)((d + 1) & ~1) + 20 * (size_t)kpp;
 }
 
-int rescore(const double* q64, int64_t B, int32_t d, const void* cat, int dtype, int64_t ld,
-            const double* gnorm, int64_t row_offset, const float* cand_vals,
-            const int64_t* cand_rows, int32_t kprime, int32_t k, int64_t n_rows, const float* eps,
-            const double* t_floor, double* out_s, int64_t* out_r, int32_t* certified,
-            hipStream_t st, const int* ovf_cnt, int ovf_cap, unsigned long long* gathered,
-            int64_t list_base, const float* theta, const int64_t* excl_off,
-            const int64_t* excl_rows, const ShardPackOut* pack) {
+int rescore(const double* q64, int64_t B, const CatOps& c, const CandList& l, int32_t k,
+            const float* eps, const double* t_floor, double* out_s, int64_t* out_r,
+            int32_t* certified, const RescoreExtras& x, hipStream_t st) {
+  // the kernels' operands under the names their launches use
+  const void* cat = c.cat;
+  const int dtype = c.dtype, d = c.d;
+  const int64_t ld = c.ld, row_offset = c.row_offset, n_rows = c.n_rows;
+  const double* gnorm = c.gnorm64;
+  const auto [cand_vals, cand_rows, kprime, list_base] = l;
+  const auto [ovf_cnt, theta, excl, pack, gathered] = x;
+  const auto [excl_off, excl_rows] = excl;
+  const int ovf_cap = 0;  // flags, not counts: any nonzero entry is an overflow
   const ShardPackOut po = pack ? *pack : ShardPackOut{};
   if (!q64 || !cat || !gnorm || !cand_vals || !cand_rows || !eps || !out_s || !out_r ||
       !certified || B < 0 || d <= 0 || ld < d || k < 1 || kprime < k || kprime > 4096 ||

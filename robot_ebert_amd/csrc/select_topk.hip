@@ -724,11 +724,11 @@ static size_t merge_lds_dyn() {
   return dyn;
 }
 
-static int merge_segment_part(float* fv, int64_t* fi, int64_t B, int kprime,
-                              const uint64_t* cand, int64_t ld_cand, int slots,
-                              const uint8_t* counts, int64_t ld_counts, int64_t n_groups,
-                              int64_t row_offset, const int64_t* eo, const int64_t* er, int* ovf,
+static int merge_segment_part(float* fv, int64_t* fi, int64_t B, int kprime, const HitSlots& h,
+                              int64_t n_groups, int64_t row_offset, const ExclCsr& excl, int* ovf,
                               hipStream_t st, double expect_hits) {
+  const auto [cand, ld_cand, slots, counts, ld_counts] = h;
+  const auto [eo, er] = excl;
   const int P_max = merge_entries(kprime);
   // LDS: the P entries, then the u16 group positions (n_groups + 1)
   const size_t gb_bytes = ((size_t)(n_groups + 1) * 2 + 15) & ~(size_t)15;
@@ -776,14 +776,11 @@ static int merge_segment_part(float* fv, int64_t* fi, int64_t B, int kprime,
 // P_max entries): merge them in consecutive parts of whole 16-group blocks. Each part merges
 // the list with the hits of its groups, so the parts together give the k' best of the list and
 // every hit -- the same (key, row) composites, hence the same list, as one merge.
-int merge_segment(float* fv, int64_t* fi, int64_t B, int kprime, const uint64_t* cand,
-                  int64_t ld_cand, int slots, const uint8_t* counts, int64_t ld_counts,
-                  int64_t n_groups,
-                  int64_t row_offset, const int64_t* eo, const int64_t* er, int* ovf,
+int merge_segment(float* fv, int64_t* fi, int64_t B, int kprime, const HitSlots& h,
+                  int64_t n_groups, int64_t row_offset, const ExclCsr& excl, int* ovf,
                   hipStream_t st, double expect_hits) {
   if (B < 0 || B > 0x7fffffffLL || kprime < 1 || kprime > KPRIME_MAX || n_groups < 1 ||
-      n_groups > 0x7fffffffLL || ld_counts < n_groups ||
-      ld_cand < n_groups * slots) {
+      n_groups > 0x7fffffffLL || h.ld_counts < n_groups || h.ld_cand < n_groups * h.slots) {
     set_error("merge_segment: bad arguments");
     return EBT_EINVAL;
   }
@@ -791,9 +788,8 @@ int merge_segment(float* fv, int64_t* fi, int64_t B, int kprime, const uint64_t*
   const int64_t part = merge_block_max_groups(kprime) & ~(int64_t)15;
   for (int64_t g0 = 0; g0 < n_groups; g0 += part) {
     const int64_t ng = n_groups - g0 < part ? n_groups - g0 : part;
-    const int rc = merge_segment_part(fv, fi, B, kprime, cand + g0 * slots, ld_cand, slots,
-                                      counts + g0, ld_counts, ng, row_offset, eo, er, ovf, st,
-                                      expect_hits * (double)ng / (double)n_groups);
+    const int rc = merge_segment_part(fv, fi, B, kprime, from_group(h, g0), ng, row_offset, excl,
+                                      ovf, st, expect_hits * (double)ng / (double)n_groups);
     if (rc) return rc;
   }
   return EBT_OK;
@@ -1347,26 +1343,27 @@ int64_t merge_block_max_groups(int kprime) {
 int64_t merge_wave_max_groups() { return 64 * 16 * WCNT; }
 int merge_wave_capacity() { return WTOP_N; }
 
-int merge_segment_wave(float* fv, int64_t* fi, int64_t B, int kprime, int k, const uint64_t* cand,
-                       int64_t ld_cand, int slots, const uint8_t* counts, int64_t ld_counts,
-                       int64_t n_groups, int64_t row_offset, const int64_t* eo,
-                       const int64_t* er, int* ovf, hipStream_t st, const float* veps,
-                       const float* vspec, float* fout, int fw, const float* feps,
-                       float* tout, const float* tin, const float* teps, int64_t B_pad) {
+int merge_segment_wave(float* fv, int64_t* fi, int64_t B, int kprime, int k, const HitSlots& h,
+                       int64_t n_groups, int64_t row_offset, const ExclCsr& excl, int* ovf,
+                       hipStream_t st, const WaveMergeOpts& o) {
+  const auto& v = o.verify;
+  const auto& f = o.floor;
+  const auto& t = o.raise;
   if (B < 0 || kprime < 1 || kprime > WMERGE_K || k < 1 || k > kprime || n_groups < 1 ||
-      (fout && (fw < 1 || fw > k)) || (tout && (!teps || B_pad < B)) ||
-      n_groups > 64 * 16 * WCNT ||
-      ld_counts < n_groups || ld_counts % 16 != 0 || ((uintptr_t)counts & 15) ||
-      ld_cand < n_groups * slots) {
+      (v.theta_spec && !v.eps) || (f.out && (f.width < 1 || f.width > k)) ||
+      (t.out && (!t.eps || t.B_pad < B)) || n_groups > 64 * 16 * WCNT ||
+      h.ld_counts < n_groups || h.ld_counts % 16 != 0 || ((uintptr_t)h.counts & 15) ||
+      h.ld_cand < n_groups * h.slots) {
     set_error("merge_segment_wave: bad arguments");
     return EBT_EINVAL;
   }
-  const int64_t nq = tout ? B_pad : B;  // waves past B only write the padding's threshold
+  const int64_t nq = t.out ? t.B_pad : B;  // waves past B only write the padding's threshold
   if (nq == 0) return EBT_OK;
   hipLaunchKernelGGL(merge_wave_kernel<false>, dim3((unsigned)ceil_div(nq, WMERGE_Q)),
-                     dim3(STHREADS), 0, st, fv, fi, B, kprime, k, cand, ld_cand, slots, counts, ld_counts, (int)n_groups, nullptr,
-                     0, 0, 0, row_offset, eo, er, ovf, veps, vspec, fout, fw, feps, tout, tin, teps,
-                     B_pad);
+                     dim3(STHREADS), 0, st, fv, fi, B, kprime, k, (const uint64_t*)h.cand,
+                     h.ld_cand, h.slots, (const uint8_t*)h.counts, h.ld_counts, (int)n_groups,
+                     nullptr, 0, 0, 0, row_offset, excl.off, excl.rows, ovf, v.eps, v.theta_spec,
+                     f.out, f.width, f.eps, t.out, t.in, t.eps, t.B_pad);
   return launch_check("merge_wave_kernel");
 }
 
@@ -1569,19 +1566,29 @@ __global__ __launch_bounds__(256) void pool_kth_kernel(const float* __restrict__
   if (lane == 0) thr[b] = th;
   if (la.lead > 0) lead_hits_wave(la, b, th, ovf, lb);
 }
+// the lead's scores and the slots its hits go to, as the kernels take them
+static bool lead_fits(const LeadIn& l, const HitSlots& h) {
+  return l.scores && l.ld >= 256 * l.tiles && h.cand && h.slots >= 1 &&
+         h.ld_cand >= l.tiles * h.slots && h.counts && h.ld_counts >= l.tiles;
+}
+static LeadArgs lead_args(const LeadIn& l, const HitSlots& h) {
+  const int tiles = l.tiles > 0 ? (int)l.tiles : 0;
+  return {l.scores, l.ld, tiles, h.cand, h.ld_cand, h.slots, h.counts, h.ld_counts};
+}
+
 int pool_kth(const float* pool, int64_t ld, int64_t B, int64_t B_pad, int G, int j, float* thr,
-             hipStream_t st, float* fv, int64_t* fi, int kprime, int* ovf,
-             const float* lead_s, int64_t ld_lead, int lead, uint64_t* cand, int64_t ld_cand,
-             int slots, uint8_t* counts, int64_t ld_counts, int gj, int64_t rstride) {
+             float* fv, int64_t* fi, int kprime, int* ovf, const LeadIn& lead, const HitSlots& h,
+             const GatheredSamples& gs, hipStream_t st) {
+  const auto [gj, rstride] = gs;
   if (!pool || !thr || B < 0 || B_pad < B || G < 1 || G > 2048 || j < 1 ||
       (gj > 0 ? (G % gj != 0 || rstride < B * (int64_t)gj) : ld < G) ||
       (fv && (!fi || !ovf || kprime < 1)) ||
-      (lead > 0 && (!lead_s || ld_lead < 256LL * lead || !cand || slots < 1 ||
-                    ld_cand < (int64_t)lead * slots || !counts || ld_counts < lead || !ovf))) {
-    set_error("pool_kth: bad arguments (G=%d j=%d ld=%lld lead=%d)", G, j, (long long)ld, lead);
+      (lead.tiles > 0 && (!lead_fits(lead, h) || !ovf))) {
+    set_error("pool_kth: bad arguments (G=%d j=%d ld=%lld lead=%d)", G, j, (long long)ld,
+              (int)lead.tiles);
     return EBT_EINVAL;
   }
-  LeadArgs la{lead_s, ld_lead, lead > 0 ? lead : 0, cand, ld_cand, slots, counts, ld_counts};
+  const LeadArgs la = lead_args(lead, h);
   const dim3 grid((unsigned)ceil_div(B_pad, 4)), block(256);
   if (G <= 256)
     hipLaunchKernelGGL(pool_kth_kernel<4>, grid, block, 0, st, pool, ld, B, B_pad, G, j, thr, fv,
@@ -1639,16 +1646,14 @@ __global__ __launch_bounds__(256) void spec_given_lead_kernel(const float* __res
 }
 
 int spec_given_init(const float* theta, int64_t B, int64_t B_pad, float* tspec, float* fv,
-                    int64_t* fi, int kprime, int* ovf, hipStream_t st, const float* lead_s,
-                    int64_t ld_lead, int lead, uint64_t* cand, int64_t ld_cand, int slots,
-                    uint8_t* counts, int64_t ld_counts) {
-  if (lead > 0) {
-    if (!lead_s || ld_lead < 256LL * lead || !cand || slots < 1 ||
-        ld_cand < (int64_t)lead * slots || !counts || ld_counts < lead) {
-      set_error("spec_given_init: bad lead arguments (lead=%d)", lead);
+                    int64_t* fi, int kprime, int* ovf, const LeadIn& lead, const HitSlots& h,
+                    hipStream_t st) {
+  if (lead.tiles > 0) {
+    if (!lead_fits(lead, h)) {
+      set_error("spec_given_init: bad lead arguments (lead=%d)", (int)lead.tiles);
       return EBT_EINVAL;
     }
-    LeadArgs la{lead_s, ld_lead, lead, cand, ld_cand, slots, counts, ld_counts};
+    const LeadArgs la = lead_args(lead, h);
     hipLaunchKernelGGL(spec_given_lead_kernel, dim3((unsigned)ceil_div(B_pad, 4)), dim3(256), 0,
                        st, theta, B, B_pad, tspec, fv, fi, kprime, ovf, la);
     return launch_check("spec_given_lead_kernel");

@@ -361,20 +361,23 @@ int ebt_cosine_topk_sharded_weighted_submit(
   // shared threshold the screen's last wave merge also writes this shard's floor entries,
   // step 4's send buffer: no ebt_floor_pack launch)
   float* fsend = (float*)(ws + S.off_fsend);
-  if (use_theta)
-    rc = screen_at_local(q64, qimg, qscale, qeps, B, L.B_pad, c.data, c.dtype, c.ld, c.gnorm64,
-                         c.image, c.cscale, c.img_dtype, c.ld_img, c.n, c.d, c.d_pad,
-                         c.row_offset, excl_off, excl_rows, L.k_eff, L.kprime, L.chunk,
-                         ws + S.off_spass, S.screen_bytes, lv, lr, recv_s, B * S.GJ,
-                         (int)(R * S.GJ), (int)S.GJ, j_s, hits, S.lead,
-                         (const float*)(ws + S.off_lead), S.ld_lead, &theta, &ovf_p, &eps_p,
-                         timer, st, fsend, (int)S.fw);
-  else
-    rc = ebt_cosine_screen(q64, qimg, qscale, qeps, B, L.B_pad, c.data, c.dtype, c.ld, c.gnorm64,
-                           c.image, c.cscale, c.img_dtype, c.ld_img, c.n, c.d, c.d_pad,
-                           c.row_offset, excl_off, excl_rows, L.k_eff, L.kprime, L.chunk,
-                           L.flags, ws + S.off_spass, S.screen_bytes, lv, lr, ovf, eps, timer,
-                           st);
+  const CatOps co = cat_ops(c);
+  const ExclCsr excl{excl_off, excl_rows};
+  PipeArgs a{{q64, qimg, qscale, qeps, B, L.B_pad}, co, excl, L.k_eff, L.kprime, L.chunk, L.flags};
+  if (use_theta) {
+    a.hits = hits;
+    a.lead = {(const float*)(ws + S.off_lead), S.ld_lead, S.lead};
+    a.gsamp = recv_s;
+    a.gs = {(int)S.GJ, B * S.GJ};
+    a.gs_G = (int)(R * S.GJ);
+    a.gs_j = j_s;
+    a.floor_out = fsend;
+    a.floor_w = (int)S.fw;
+    rc = screen_at_local(a, ws + S.off_spass, S.screen_bytes, lv, lr, &theta, &ovf_p, &eps_p,
+                         timer, st);
+  } else {
+    rc = screen_export(a, ws + S.off_spass, S.screen_bytes, lv, lr, ovf, eps, timer, st);
+  }
   if (rc) return rc;
   // 4. the catalog-wide floor: the k-th largest (approx - eps) over every shard's fw best
   float* frecv = (float*)(ws + S.off_frecv);
@@ -411,10 +414,9 @@ int ebt_cosine_topk_sharded_weighted_submit(
   // shard's entries above the floor for the results exchange: ebt_shard_pack's two launches
   // folded in; the finish packs again only for a batch whose retries changed lists)
   const ShardPackOut pack{S.cap && !padded ? (uint32_t*)(ws + S.off_psend) + B : nullptr};
-  rc = rescore_sharded(q64, B, c.d, c.data, c.dtype, c.ld, c.gnorm64, c.row_offset, lv, lr,
-                       L.kprime, L.k_eff, c.n, eps_p, tfloor, rs, rr, cert, ovf_p,
-                       use_theta ? theta : nullptr, timer, st, use_theta ? 0 : c.row_offset,
-                       excl_off, excl_rows, &pack);
+  rc = rescore_sharded(q64, B, co, {lv, lr, L.kprime, use_theta ? 0 : c.row_offset}, L.k_eff,
+                       eps_p, tfloor, rs, rr, cert,
+                       {ovf_p, use_theta ? theta : nullptr, excl, &pack, nullptr}, timer, st);
   if (rc) return rc;
   // the certificates to the caller's host buffer (unless the rescore wrote them there); one
   // event for them

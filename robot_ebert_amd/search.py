@@ -253,6 +253,16 @@ def csr_subset(off: torch.Tensor, rows: torch.Tensor, idx: torch.Tensor):
     return new_off, rows.index_select(0, starts.index_select(0, seg) + pos)
 
 
+def _dense_queries(queries: torch.Tensor, d: int) -> torch.Tensor:
+    """A dense query batch as the C entries take it: CUDA [B, d], supported dtype, unit stride."""
+    require_cuda(queries, "queries")
+    if queries.dim() != 2 or queries.shape[1] != d:
+        raise EbertError(f"queries must be [B, {d}], got {tuple(queries.shape)}")
+    if queries.dtype not in DTYPE_CODE:
+        raise EbertError(f"unsupported query dtype {queries.dtype}")
+    return queries if queries.stride(1) == 1 else queries.contiguous()
+
+
 def prepare_queries(catalog: Catalog, queries: Optional[torch.Tensor] = None,
                     liked: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                     liked_counts: Optional[torch.Tensor] = None,
@@ -278,13 +288,7 @@ def prepare_queries(catalog: Catalog, queries: Optional[torch.Tensor] = None,
         raise EbertError("pass exactly one of queries= or liked=")
     native_q = False
     if queries is not None:
-        require_cuda(queries, "queries")
-        if queries.dim() != 2 or queries.shape[1] != d:
-            raise EbertError(f"queries must be [B, {d}], got {tuple(queries.shape)}")
-        if queries.dtype not in DTYPE_CODE:
-            raise EbertError(f"unsupported query dtype {queries.dtype}")
-        if queries.stride(1) != 1:
-            queries = queries.contiguous()
+        queries = _dense_queries(queries, d)
         B = int(queries.shape[0])
         q64 = torch.empty((B, d), dtype=torch.float64, device=dev)
         native_q = catalog.native and queries.dtype == catalog.img_torch_dtype
@@ -355,6 +359,12 @@ def default_kprime(catalog: Catalog, k: int) -> int:
     return min(_round_up(kp, 8), KPRIME_MAX)
 
 
+def _clamp_kprime(catalog: Catalog, k_eff: int, kprime: Optional[int] = None) -> int:
+    """k' (default: default_kprime) as a multiple of 4 in [k_eff, min(catalog rows, KPRIME_MAX)]."""
+    kp = kprime or default_kprime(catalog, k_eff)
+    return max(_round_up(k_eff, 4), min(_round_up(kp, 4), _round_up(catalog.n, 4), KPRIME_MAX))
+
+
 def _chunk_rows(catalog: Catalog, B_pad: int, budget: int) -> int:
     rows = budget // (4 * B_pad)
     rows = max(128, rows // 128 * 128)
@@ -369,8 +379,7 @@ def plan(catalog: Catalog, B: int, k: int, kprime: Optional[int] = None,
     import ctypes
     B_pad = pad_batch(B)
     k_eff = min(k, catalog.n)
-    kp = kprime or default_kprime(catalog, k_eff)
-    kp = max(_round_up(k_eff, 4), min(_round_up(kp, 4), _round_up(catalog.n, 4), KPRIME_MAX))
+    kp = _clamp_kprime(catalog, k_eff, kprime)
     chunk = chunk_rows or _chunk_rows(catalog, B_pad, DEFAULT_SCORE_BUDGET)
     h, c, ch = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
     f = ctypes.c_int32()
@@ -400,6 +409,30 @@ def spec_plan(B: int, n: int, kprime: int, fuse: bool = True) -> Optional[dict]:
             "lead": lead}
 
 
+def _pipe_operands(catalog: Catalog, qb: QueryBatch, exclude, k: int, kprime: int, chunk: int,
+                   flags: int) -> tuple:
+    """The 24 operands every prepared / screen entry of ebert.h starts with, in its order."""
+    eo, er = exclude if exclude is not None else (None, None)
+    return (ptr(qb.q64), ptr(qb.qimg), ptr(qb.qscale), ptr(qb.eps), qb.B, qb.B_pad,
+            ptr(catalog.data), catalog.dtype_code, catalog.ld, ptr(catalog.gnorm),
+            ptr(catalog.image), ptr(catalog.cscale), catalog.img_dtype, catalog.ld_img, catalog.n,
+            catalog.d, catalog.d_pad, catalog.row_offset, ptr(eo), ptr(er), k, kprime, chunk,
+            flags)
+
+
+def _pipe_buffers(catalog: Catalog, qb: QueryBatch, kprime: int, chunk_rows: Optional[int],
+                  flags: int, workspace: Optional[torch.Tensor] = None):
+    """(chunk rows, workspace) of one prepared / screen call: the workspace sized by
+    ebt_cosine_topk_workspace for `flags` (the caller's if it is large enough)."""
+    chunk = chunk_rows or _chunk_rows(catalog, qb.B_pad, DEFAULT_SCORE_BUDGET)
+    need = _lib.load().ebt_cosine_topk_workspace(qb.B, qb.B_pad, catalog.n, kprime, chunk, flags)
+    if need == 0:
+        raise EbertError("invalid workspace request")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=catalog.device)
+    return chunk, workspace
+
+
 def run_pipeline(catalog: Catalog, qb: QueryBatch, k: int, kprime: int,
                  exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                  chunk_rows: Optional[int] = None, timer: Optional[_lib.Timer] = None,
@@ -411,27 +444,17 @@ def run_pipeline(catalog: Catalog, qb: QueryBatch, k: int, kprime: int,
     import ctypes
     from .allow import resolve_allow
     dev = catalog.device
-    st = stream_of(dev)
-    B, B_pad = qb.B, qb.B_pad
+    B = qb.B
     ra = resolve_allow(allow, B, dev)
     if ra is not None and not flags & _lib.EBT_FLAG_EXACT:
         flags |= _lib.EBT_FLAG_NO_FUSE
-    chunk = chunk_rows or _chunk_rows(catalog, B_pad, DEFAULT_SCORE_BUDGET)
-    need = _lib.load().ebt_cosine_topk_workspace(B, B_pad, catalog.n, kprime, chunk, flags)
-    if need == 0:
-        raise EbertError("invalid workspace request")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    chunk, workspace = _pipe_buffers(catalog, qb, kprime, chunk_rows, flags, workspace)
     out_s = torch.empty((B, k), dtype=torch.float64, device=dev)
     out_r = torch.empty((B, k), dtype=torch.int64, device=dev)
     cert = torch.empty(B, dtype=torch.int32, device=dev)
-    eo, er = (exclude if exclude is not None else (None, None))
-    args = (ptr(qb.q64), ptr(qb.qimg), ptr(qb.qscale), ptr(qb.eps), B, B_pad,
-            ptr(catalog.data), catalog.dtype_code, catalog.ld, ptr(catalog.gnorm), ptr(catalog.image),
-            ptr(catalog.cscale), catalog.img_dtype, catalog.ld_img, catalog.n, catalog.d,
-            catalog.d_pad, catalog.row_offset, ptr(eo), ptr(er), k, kprime, chunk, flags,
+    args = (*_pipe_operands(catalog, qb, exclude, k, kprime, chunk, flags),
             ptr(workspace), int(workspace.numel()), ptr(out_s), ptr(out_r), ptr(cert),
-            timer.handle if timer is not None else None, st)
+            timer.handle if timer is not None else None, stream_of(dev))
     if ra is None:
         call("ebt_cosine_topk_prepared", *args)
     else:
@@ -445,25 +468,24 @@ def run_screen(catalog: Catalog, qb: QueryBatch, k: int, kprime: int,
                flags: int = 0):
     """Phase 1 of the two-phase sharded top-k (ebt_cosine_screen): this shard's k' best approx
     candidates. Returns (vals f32 [B,k'], GLOBAL rows i64 [B,k'], ovf i32 [B], eps f32 [B])."""
-    dev = catalog.device
-    B, B_pad = qb.B, qb.B_pad
-    chunk = chunk_rows or _chunk_rows(catalog, B_pad, DEFAULT_SCORE_BUDGET)
-    need = _lib.load().ebt_cosine_topk_workspace(B, B_pad, catalog.n, kprime, chunk, flags)
-    if need == 0:
-        raise EbertError("invalid workspace request")
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    lv = torch.empty((B, kprime), dtype=torch.float32, device=dev)
-    lr = torch.empty((B, kprime), dtype=torch.int64, device=dev)
-    ovf = torch.empty(B, dtype=torch.int32, device=dev)
-    eps = torch.empty(B, dtype=torch.float32, device=dev)
-    eo, er = (exclude if exclude is not None else (None, None))
-    call("ebt_cosine_screen", ptr(qb.q64), ptr(qb.qimg), ptr(qb.qscale), ptr(qb.eps), B, B_pad,
-         ptr(catalog.data), catalog.dtype_code, catalog.ld, ptr(catalog.gnorm), ptr(catalog.image),
-         ptr(catalog.cscale), catalog.img_dtype, catalog.ld_img, catalog.n, catalog.d,
-         catalog.d_pad, catalog.row_offset, ptr(eo), ptr(er), k, kprime, chunk, flags, ptr(ws),
-         int(ws.numel()), ptr(lv), ptr(lr), ptr(ovf), ptr(eps),
-         timer.handle if timer is not None else None, stream_of(dev))
-    return lv, lr, ovf, eps
+    return _screen("ebt_cosine_screen", catalog, qb, k, kprime, exclude, chunk_rows, timer, flags,
+                   flags, ())
+
+
+def _screen(entry: str, catalog: Catalog, qb: QueryBatch, k: int, kprime: int, exclude,
+            chunk_rows: Optional[int], timer: Optional[_lib.Timer], flags: int, ws_flags: int,
+            extra: tuple):
+    """One call of a screen entry (ebt_cosine_screen, or with extra = (theta, hits)
+    ebt_cosine_screen_at, whose workspace is sized with ws_flags = EBT_FLAG_THETA): its workspace
+    and outputs (vals f32 [B,k'], rows i64 [B,k'], ovf i32 [B], eps f32 [B])."""
+    chunk, ws = _pipe_buffers(catalog, qb, kprime, chunk_rows, ws_flags)
+    outs = tuple(torch.empty(s, dtype=t, device=catalog.device) for s, t in (
+        ((qb.B, kprime), torch.float32), ((qb.B, kprime), torch.int64), (qb.B, torch.int32),
+        (qb.B, torch.float32)))
+    call(entry, *_pipe_operands(catalog, qb, exclude, k, kprime, chunk, flags), ptr(ws),
+         int(ws.numel()), *(ptr(t) for t in outs), *extra,
+         timer.handle if timer is not None else None, stream_of(catalog.device))
+    return outs
 
 
 def spec_rank(lam: float, tail: float = 1e-6) -> int:
@@ -508,26 +530,9 @@ def screen_at(catalog: Catalog, qb: QueryBatch, k: int, kprime: int, theta: torc
               chunk_rows: Optional[int] = None, timer: Optional[_lib.Timer] = None):
     """ebt_cosine_screen_at: run_screen at the caller's threshold theta [B_pad] f32 (see
     include/ebert.h: the caller verifies theta against the catalog-wide floor)."""
-    dev = catalog.device
-    B, B_pad = qb.B, qb.B_pad
-    chunk = chunk_rows or _chunk_rows(catalog, B_pad, DEFAULT_SCORE_BUDGET)
-    need = _lib.load().ebt_cosine_topk_workspace(B, B_pad, catalog.n, kprime, chunk,
-                                                 _lib.EBT_FLAG_THETA)
-    if need == 0:
-        raise EbertError("invalid workspace request")
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    lv = torch.empty((B, kprime), dtype=torch.float32, device=dev)
-    lr = torch.empty((B, kprime), dtype=torch.int64, device=dev)
-    ovf = torch.empty(B, dtype=torch.int32, device=dev)
-    eps = torch.empty(B, dtype=torch.float32, device=dev)
-    eo, er = (exclude if exclude is not None else (None, None))
-    call("ebt_cosine_screen_at", ptr(qb.q64), ptr(qb.qimg), ptr(qb.qscale), ptr(qb.eps), B,
-         B_pad, ptr(catalog.data), catalog.dtype_code, catalog.ld, ptr(catalog.gnorm),
-         ptr(catalog.image), ptr(catalog.cscale), catalog.img_dtype, catalog.ld_img, catalog.n,
-         catalog.d, catalog.d_pad, catalog.row_offset, ptr(eo), ptr(er), k, kprime, chunk, 0,
-         ptr(ws), int(ws.numel()), ptr(lv), ptr(lr), ptr(ovf), ptr(eps), ptr(theta.contiguous()),
-         float(hits), timer.handle if timer is not None else None, stream_of(dev))
-    return lv, lr, ovf, eps
+    theta = theta.contiguous()   # (named: alive until the call is enqueued)
+    return _screen("ebt_cosine_screen_at", catalog, qb, k, kprime, exclude, chunk_rows, timer, 0,
+                   _lib.EBT_FLAG_THETA, (ptr(theta), float(hits)))
 
 
 def score_topk_submit(catalog: Catalog, k: int, queries: Optional[torch.Tensor] = None,
@@ -656,13 +661,7 @@ def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_r
                    else exclude if isinstance(exclude, SortedCSR) else csr_sorted(*exclude))
     q_ptr, q_dt, ldq, lo, lr, lo_csr = None, 0, 0, None, None, None
     if queries is not None:
-        require_cuda(queries, "queries")
-        if queries.dim() != 2 or queries.shape[1] != catalog.d:
-            raise EbertError(f"queries must be [B, {catalog.d}], got {tuple(queries.shape)}")
-        if queries.dtype not in DTYPE_CODE:
-            raise EbertError(f"unsupported query dtype {queries.dtype}")
-        if queries.stride(1) != 1:
-            queries = queries.contiguous()
+        queries = _dense_queries(queries, catalog.d)
         B = int(queries.shape[0])
         q_ptr, q_dt, ldq = ptr(queries), DTYPE_CODE[queries.dtype], int(queries.stride(0))
     else:
@@ -773,16 +772,23 @@ def _submit_liked_on_view(parent: Catalog, view: Catalog, k: int, liked, exclude
     k_eff = min(k, view.n)
     if k_eff > KPRIME_MAX:
         raise EbertError(f"k={k} > {KPRIME_MAX} over a {view.n}-row sub-catalog is not supported")
-    kp = kprime or default_kprime(view, k_eff)
-    kp = max(_round_up(k_eff, 4), min(_round_up(kp, 4), n_cap, KPRIME_MAX))
+    kp = _clamp_kprime(view, k_eff, kprime)
     flags = 0 if fuse else _lib.EBT_FLAG_NO_FUSE
     s, r, cert = run_pipeline(view, qb, k_eff, kp, exclude, chunk_rows, timer, flags=flags)
+    return _pending(view, qb, k, k_eff, kp, exclude, chunk_rows, timer, flags, n_cap, s, r, cert,
+                    None)
+
+
+def _pending(catalog: Catalog, qb: QueryBatch, k, k_eff, kp, exclude, chunk_rows, timer, flags,
+             n_cap, s, r, cert, t_floor) -> "PendingTopk":
+    """The tail of a first pass: the certificates travel to pinned host memory right behind this
+    batch's kernels, so finishing it waits for this batch only, not for those submitted later."""
     cert_host = torch.empty(cert.shape, dtype=cert.dtype, pin_memory=True)
     cert_host.copy_(cert, non_blocking=True)
     ready = torch.cuda.Event()
-    ready.record(torch.cuda.current_stream(dev))
-    return PendingTopk(view, qb, k, k_eff, kp, exclude, chunk_rows, timer, flags, n_cap, s, r,
-                       cert, cert_host, ready, None)
+    ready.record(torch.cuda.current_stream(catalog.device))
+    return PendingTopk(catalog, qb, k, k_eff, kp, exclude, chunk_rows, timer, flags, n_cap, s, r,
+                       cert, cert_host, ready, t_floor)
 
 
 def _take_weights(liked, weights, idx_host, idx_dev):
@@ -918,8 +924,7 @@ def score_topk_stages(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
     k_eff = min(k, catalog.n)
     if k_eff > KPRIME_MAX:
         raise EbertError(f"k={k} > {KPRIME_MAX} over a {catalog.n}-row catalog is not supported")
-    kp = kprime or default_kprime(catalog, k_eff)
-    kp = max(_round_up(k_eff, 4), min(_round_up(kp, 4), n_cap, KPRIME_MAX))
+    kp = _clamp_kprime(catalog, k_eff, kprime)
     flags = 0 if fuse else _lib.EBT_FLAG_NO_FUSE
     t_floor = None
     if t_floor_hook is None:
@@ -934,14 +939,8 @@ def score_topk_stages(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
         next(cut)
         yield
         s, r, cert, t_floor = next(cut)
-    # the certificates travel to pinned host memory right behind this batch's kernels, so
-    # finishing it waits for this batch only, not for batches submitted after it
-    cert_host = torch.empty(cert.shape, dtype=cert.dtype, pin_memory=True)
-    cert_host.copy_(cert, non_blocking=True)
-    ready = torch.cuda.Event()
-    ready.record(torch.cuda.current_stream(dev))
-    yield PendingTopk(catalog, qb, k, k_eff, kp, exclude, chunk_rows, timer, flags, n_cap,
-                      s, r, cert, cert_host, ready, t_floor)
+    yield _pending(catalog, qb, k, k_eff, kp, exclude, chunk_rows, timer, flags, n_cap, s, r, cert,
+                   t_floor)
 
 
 def score_topk_finish(p) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -992,8 +991,7 @@ def score_topk_finish(p) -> Tuple[torch.Tensor, torch.Tensor]:
             # k-th score: screen these queries again in float64 (EBT_FLAG_EXACT), from the
             # default k' up
             flags = _lib.EBT_FLAG_EXACT
-            kp = max(_round_up(k_eff, 4), min(_round_up(default_kprime(catalog, k_eff), 4),
-                                              n_cap, KPRIME_MAX))
+            kp = _clamp_kprime(catalog, k_eff)
         sub_ex = csr_subset(exclude[0], exclude[1], bad) if exclude is not None else None
         s2, r2, c2 = run_pipeline(catalog, qb.subset(bad), k_eff, kp, sub_ex, chunk_rows, timer,
                                   flags=flags)

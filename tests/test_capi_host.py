@@ -368,3 +368,53 @@ def test_eight_gpu_memory_budget(name, N, d, es, B, k, all_reduce):
     if name == "C5":
         assert ws < 14 * 2 ** 30, ws / 2 ** 30          # was 27.76 GiB per slot (round 5)
         assert total < 70e9, total / 1e9
+
+
+def test_prepared_and_screen_entries_report_argument_errors():
+    """The five prepared / screen entries check their operands before any HIP call, each in its
+    own order and under its own name: return code and the whole ebt_last_error() text for a null
+    operand, a bad size, a null and a short workspace, and the entry's own checks. Two entries
+    report under another's name: the allowed entry without masks as ebt_cosine_topk_prepared,
+    ebt_cosine_screen_at_lead as ebt_cosine_screen_at except for its lead check. The pointers
+    are fake and never dereferenced; the workspace sizes are the layout's for this shape."""
+    from robot_ebert_amd import _lib
+    lib = _lib.load()
+    P = 1 << 30
+    n, d = 1000, 64
+
+    def operands(q64=P, B_pad=128, flags=0):
+        return [q64, P, P, P, 4, B_pad, P, _lib.EBT_F32, d, P, P, None, _lib.EBT_F16, d, n, d, d,
+                0, None, None, 2, 8, 128, flags]
+
+    # entry -> (the name it reports under, its arguments after (workspace, ws_bytes))
+    entries = {
+        "ebt_cosine_topk_prepared": ("ebt_cosine_topk_prepared", [P, P, P, None, None]),
+        "ebt_cosine_topk_prepared_allowed": ("ebt_cosine_topk_prepared",
+                                             [P, P, P, None, None, None]),
+        "ebt_cosine_screen": ("ebt_cosine_screen", [P, P, P, P, None, None]),
+        "ebt_cosine_screen_at": ("ebt_cosine_screen_at", [P, P, P, P, P, 1.0, None, None]),
+        "ebt_cosine_screen_at_lead": ("ebt_cosine_screen_at",
+                                      [P, P, P, P, P, 1.0, 0, None, 0, None, None]),
+    }
+    need = {"ebt_cosine_topk_prepared": 69120, "ebt_cosine_screen": 69120,
+            "ebt_cosine_screen_at": 1202176}
+
+    def run(entry, ops, ws, ws_bytes, tail=None):
+        rc = getattr(lib, entry)(*ops, ws, ws_bytes, *(entries[entry][1] if tail is None else tail))
+        return rc, lib.ebt_last_error().decode()
+
+    for entry, (who, _) in entries.items():
+        assert run(entry, operands(q64=None), P, 1 << 40) == (-1, f"{who}: null pointer"), entry
+        assert run(entry, operands(B_pad=100), P, 1 << 40) == (
+            -1, f"{who}: bad arguments (B=4 B_pad=100 n=1000 d=64 d_pad=64 k=2 kprime=8 "
+                f"chunk=128)"), entry
+        assert run(entry, operands(), None, 1 << 40) == (-1, f"{who}: null pointer"), entry
+        assert run(entry, operands(), P, 16) == (
+            -3, f"{who}: workspace 16 < {need[who]} bytes"), entry
+    for entry in ("ebt_cosine_screen_at", "ebt_cosine_screen_at_lead"):
+        assert run(entry, operands(flags=_lib.EBT_FLAG_NO_FUSE), P, 1 << 40) == (
+            -1, "ebt_cosine_screen_at: needs the fused screen with kprime <= 512 (kprime=8, "
+                "flags=5, hits=1)"), entry
+    assert run("ebt_cosine_screen_at_lead", operands(), P, 1 << 40,
+               [P, P, P, P, P, 1.0, 5, None, 0, None, None]) == (
+        -1, "ebt_cosine_screen_at_lead: bad lead (lead=5, ld_lead=0, n_rows=1000)")
