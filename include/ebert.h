@@ -86,7 +86,10 @@ extern "C" {
  *        ebt_sub_rows_to_global (additive; no existing entry, struct or kernel changes).
  * 0.8.0: per-row weights on liked-row queries: ebt_query_liked_wsum, ebt_cosine_topk_weighted /
  *        _weighted_submit, ebt_cosine_topk_sharded_weighted / _sharded_weighted_submit
- *        (additive; liked_w == NULL launches the kernels of 0.7.0; no workspace size changes). */
+ *        (additive; liked_w == NULL launches the kernels of 0.7.0; no workspace size changes).
+ * 0.9.0: explanations, the per-liked-row terms of a returned score: ebt_explain_workspace_bytes,
+ *        ebt_liked_contrib, ebt_explain_select, ebt_explain_topk (additive; no existing kernel,
+ *        struct, signature or workspace size changes). */
 int ebt_version(void);
 
 /* Message for the last non-zero return on this thread ("" if none). */
@@ -912,6 +915,61 @@ int ebt_cosine_topk_sharded_weighted_submit(
     const int64_t* excl_off, const int64_t* excl_rows, const ebt_options* opt, void* workspace,
     size_t ws_bytes, double* out_scores, int64_t* out_rows, int32_t* host,
     ebt_sharded_pending* pending, void* timer, void* stream, const double* liked_w);
+
+/* ---- explanations (0.9.0): the per-liked-row contributions to each returned score -----------
+ * The reference scores a user by cosine_similarity(catalog.loc[liked], catalog).mean(axis=0)
+ * (lib.py:51-52): a returned score is a sum of one term per liked row,
+ *   score_b(j) = sum_l contrib(b, j, l),
+ *   contrib(b, j, l) = ( w_l * ( (x_{r_l} . x_j) / (g_{r_l} * g_j) ) ) * (1 / W_b),
+ * with w_l = 1 and W_b = L_b unweighted, W_b = sum_l |w_l| with weights (0.8.0). The search
+ * entries fold the liked rows into one query vector before their GEMM and never hold the terms;
+ * these entries compute them afterwards for the rows a search returned -- the reference's matrix
+ * pairwise_similarities restricted to the returned columns, before .mean, times w_l / W_b -- and
+ * pick the m largest (or smallest) per returned row: "because you liked X and Y", "despite Z".
+ *
+ * Inputs: the liked CSR of the search (liked_off [B + 1], liked_rows, liked_w or NULL; GLOBAL
+ * rows, any order, a row may repeat: every entry is its own term) and rows [B][k], the GLOBAL
+ * result rows (-1 = an empty slot), all of ONE unsharded catalog: rows [row_offset,
+ * row_offset + n). Results of masked and sub-catalog searches qualify (they are parent rows).
+ *
+ * ebt_liked_contrib: out[k * liked_off[b] + j * L_b + l] = contrib(b, j, l), l the position in
+ * query b's list (a CSR-shaped matrix: k * nnz float64 in all). All arithmetic is float64; g is
+ * the catalog's guarded gnorm64, so a zero-norm row contributes exactly 0 (sklearn); W_b is the
+ * sequential sum of |w_l| in CSR order, as in 0.8.0, and the four operations of the formula are
+ * rounded one at a time in the order written. The dot products run on the float64 MFMA in a
+ * fixed order that depends on d and the dtype only (csrc/explain.hip), so query b's values are
+ * bitwise the same alone or in any batch, with weights 1.0 or liked_w == NULL, and under any
+ * power-of-two scaling of the weights. Empty result slots give NaN. A liked or result row outside
+ * the catalog is never read: status[b] = -2 and every output of that query is NaN; otherwise
+ * status[b] = 1 (device int32 [B]; nothing is read back, the call only enqueues).
+ *
+ * ebt_explain_select: from each (b, j) segment of L_b values, the m best in the order (value
+ * desc, position asc), or (value asc, position asc) with largest == 0; -0 equals +0; a NaN is
+ * never selected. out_val [B][k][m] float64 (NaN padded), out_pos [B][k][m] int32 position in
+ * query b's list (-1 padded; the unambiguous handle when a list repeats a row), out_row
+ * [B][k][m] int64 = liked_rows at that position (-1 padded), out_total [B][k] = the sequential
+ * float64 sum of the segment in list order (NULL: not computed). 1 <= m <= EBT_EXPLAIN_M_MAX.
+ *
+ * ebt_explain_topk: the two above over a caller's workspace of ebt_explain_workspace_bytes(nnz, k)
+ * bytes (the matrix: 8 * k * nnz rounded up to 256, at least 256; 0 for nnz < 0 or k < 1), nnz =
+ * liked_off[B] as the caller knows it on the host.
+ *
+ * Found on the host before any GPU call, EBT_EINVAL with a message: a null pointer, k < 1, m out
+ * of range, a workspace that is too small. No timer stage is recorded. */
+#define EBT_EXPLAIN_M_MAX 64
+size_t ebt_explain_workspace_bytes(int64_t nnz, int32_t k);
+int ebt_liked_contrib(const ebt_catalog* cat, int64_t B, const int64_t* liked_off,
+                      const int64_t* liked_rows, const double* liked_w, const int64_t* rows,
+                      int32_t k, double* out, int32_t* status, void* stream);
+int ebt_explain_select(const double* contrib, int64_t B, const int64_t* liked_off,
+                       const int64_t* liked_rows, int32_t k, int32_t m, int largest,
+                       double* out_val, int32_t* out_pos, int64_t* out_row, double* out_total,
+                       void* stream);
+int ebt_explain_topk(const ebt_catalog* cat, int64_t B, const int64_t* liked_off,
+                     const int64_t* liked_rows, const double* liked_w, int64_t nnz,
+                     const int64_t* rows, int32_t k, int32_t m, int largest, void* workspace,
+                     size_t ws_bytes, double* out_val, int32_t* out_pos, int64_t* out_row,
+                     double* out_total, int32_t* status, void* stream);
 
 /* ---- two-phase top-k over a row-sharded catalog (robot_ebert_amd/distributed.py) ---------
  * Phase 1, every rank: ebt_cosine_screen = ebt_cosine_topk_prepared without the rescore: the shard's k'

@@ -19,12 +19,16 @@ with the same rows and bitwise the same scores.
 Liked rows can carry weights (ABI 0.8.0): ``score_topk(..., liked=, liked_weights=)`` scores by
 sum_l w_l cos(x_l, x) / sum_l |w_l| (negative weights push away), through every path the
 unweighted call has; ``lib.get_user_recs(..., weighting=)`` maps a user's ratings to weights.
+
+``explain_topk`` (ABI 0.9.0) says why: for the rows a search returned, the per-liked-row terms of
+each score and the m largest of them; ``lib.get_user_recs_explained`` attaches them as reasons.
 """
 from ._lib import EbertError, Timer, load  # noqa: F401
 from .catalog import Catalog  # noqa: F401
 from .allow import AllowMasks, SubCatalog  # noqa: F401
 from .search import (merge_topk, prepare_queries, rescore_rows, score_topk,  # noqa: F401
                      score_topk_finish, score_topk_submit)
+from .explain import Explanation, explain_topk  # noqa: F401
 from . import ops  # noqa: F401,E402  (registers torch.ops.ebert.*)
 
 __version__ = "0.1.0"

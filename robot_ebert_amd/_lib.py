@@ -26,6 +26,7 @@ EBT_FLAG_EXACT = 2
 EBT_FLAG_THETA = 4
 EBT_FLAG_LIKED_CHECKED = 8   # ebert.h: the liked CSR was checked on the host (no read-back)
 EBT_FILTER_SLOTS_MAX = 128
+EBT_EXPLAIN_M_MAX = 64       # ebert.h: the most reasons ebt_explain_select returns per row
 
 
 class EbertError(RuntimeError):
@@ -141,6 +142,12 @@ _SIGNATURES = {
     "ebt_sub_exclusions": ([_VP, _I64, _VP, _I64, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _SZ, _VP],
                            _INT),
     "ebt_sub_rows_to_global": ([_VP, _I64, _VP, _I64, _VP], _INT),
+    "ebt_explain_workspace_bytes": ([_I64, _I32], _SZ),
+    "ebt_liked_contrib": ([_PCAT, _I64, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP], _INT),
+    "ebt_explain_select": ([_VP, _I64, _VP, _VP, _I32, _I32, _INT, _VP, _VP, _VP, _VP, _VP],
+                           _INT),
+    "ebt_explain_topk": ([_PCAT, _I64, _VP, _VP, _VP, _I64, _VP, _I32, _I32, _INT, _VP, _SZ,
+                          _VP, _VP, _VP, _VP, _VP, _VP], _INT),
     "ebt_sharded_workspace_bytes": ([_PCAT, _PCOMM, _I64, _I32, _POPT], _SZ),
     "ebt_cosine_topk_sharded": ([_PCAT, _PCOMM, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP,
                                  _POPT, _VP, _SZ, _VP, _VP, _VP, _VP], _INT),

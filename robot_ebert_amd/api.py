@@ -16,7 +16,7 @@ from typing import List
 from fastapi import APIRouter, FastAPI
 
 from . import lib
-from .models import Recommendation
+from .models import ExplainedRecommendation, Recommendation
 
 router = APIRouter()
 # a batcher.RecBatcher installed by app(batcher=...): the handler's scoring step is then
@@ -31,6 +31,14 @@ def get_user_recommendations(user_id: str, k: int = 10) -> List[Recommendation]:
         return lib.get_user_recs_batched(_batcher, user_id=user_id, k=k)
     user_recommendations = lib.get_user_recs(user_id=user_id, k=k)
     return user_recommendations
+
+
+@router.get("/users/{user_id}/recommendations/explained/")
+def get_user_recommendations_explained(user_id: str, k: int = 10,
+                                       m: int = 3) -> List[ExplainedRecommendation]:
+    """the same recommendations, each with the m rated movies that contributed most to its score
+    (no counterpart in the reference; never batched)"""
+    return lib.get_user_recs_explained(user_id=user_id, k=k, m=m)
 
 
 def app(batcher=None) -> FastAPI:

@@ -626,7 +626,7 @@ using namespace ebt;
 
 extern "C" {
 
-int ebt_version(void) { return 800; }  // 0.8.0: per-row weights on liked-row queries (ebert.h)
+int ebt_version(void) { return 900; }  // 0.9.0: explanations, per-liked-row contributions (ebert.h)
 
 const char* ebt_last_error(void) { return g_err; }
 

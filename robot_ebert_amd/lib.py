@@ -21,7 +21,7 @@ from sqlalchemy import select
 
 from . import tables
 from .catalog import Catalog
-from .models import Movie, Recommendation
+from .models import ExplainedRecommendation, Movie, Reason, Recommendation
 from .search import csr_from_lists, prepare_queries, rescore_rows, score_topk
 
 LIKED_MOVIE_SCORE = 3.5   # constants.py:19
@@ -210,6 +210,87 @@ def get_user_recs(user_id: str, k: int = 10, allow=None,
 
 
 get_user_recs_gpu = get_user_recs  # SURVEY §8b's name for the drop-in
+
+
+def _user_terms(user_id: str, weighting: Optional[Callable[[float], float]]
+                ) -> Optional[Tuple[List[int], List[int], Optional[List[float]], List[float]]]:
+    """One fetch of what ``get_user_recs`` scores from, with the ratings kept: (liked rows, rated
+    rows, weights or None, the rating behind each liked row). The lists are ``_user_request``'s
+    (weighting None) or ``_user_request_weighted``'s, entry for entry; None when the user has no
+    ratings; sklearn's ValueError when no liked row is left."""
+    cat = movies_collab_catalog
+    with engine.begin() as cnx:  # lib.py:36-40
+        statement = select(tables.ratings).where(tables.ratings.c.user_id == user_id)
+        user_ratings = cnx.execute(statement).all()
+        if not user_ratings:
+            return None
+    pos = cat.index_pos
+    kept = [(r.tmdb_id, r.rating) for r in user_ratings if r.tmdb_id in pos]  # lib.py:44
+    if weighting is None:
+        terms = [(t, None, rt) for t, rt in kept if rt >= LIKED_MOVIE_SCORE]  # lib.py:47
+    else:
+        terms = [(t, float(weighting(rt)), rt) for t, rt in kept]
+        terms = [x for x in terms if x[1] != 0.0]
+    rated = cat.rows_of(list(dict.fromkeys(t for t, _ in kept)))              # lib.py:48
+    if not terms:  # sklearn check_pairwise_arrays on an empty X (lib.py:51)
+        raise ValueError(f"Found array with 0 sample(s) (shape=(0, {cat.d})) while a minimum of 1 "
+                         "is required by check_pairwise_arrays.")
+    return (cat.rows_of([t for t, _, _ in terms]), rated,
+            None if weighting is None else [w for _, w, _ in terms],
+            [float(rt) for _, _, rt in terms])
+
+
+def _hydrate_explained(s: np.ndarray, r: np.ndarray,
+                       reasons_by_id) -> List[ExplainedRecommendation]:
+    """``_hydrate`` with reasons. The reasons are keyed by the recommended movie's tmdb_id BEFORE
+    the sort_index / get_movies / zip of lib.py:55-62 and attached by the id of the Movie that
+    came back, never by zip position: when ``movies`` lacks a row (SURVEY a-8: 2269 collab ids,
+    2264 movie rows) the reference's zip shifts the scores, and the reasons still follow their
+    movie."""
+    cat = movies_collab_catalog
+    pairs = [(cat.id_of(int(rr)), float(ss)) for ss, rr in zip(s, r) if rr >= 0]
+    ordered_by_id = sorted(pairs, key=lambda t: t[0])  # .sort_index()
+    movies = get_movies(tmdb_ids=[t for t, _ in ordered_by_id])  # lib.py:58
+    scores_by_id = [sc for _, sc in ordered_by_id]  # lib.py:59
+    recs = [ExplainedRecommendation(movie=mv, score=sc, reasons=reasons_by_id.get(mv.tmdb_id, []))
+            for mv, sc in zip(movies, scores_by_id)]
+    return sorted(recs, key=lambda x: x.score, reverse=True)  # lib.py:63
+
+
+def get_user_recs_explained(user_id: str, k: int = 10, m: int = 3,
+                            weighting: Optional[Callable[[float], float]] = None,
+                            allow=None) -> List[ExplainedRecommendation]:
+    """``get_user_recs`` with the "because you liked" line: the same movies, scores, order and
+    errors (``[]`` for a user without ratings, sklearn's ValueError for one without a liked
+    movie), each item carrying up to ``m`` reasons -- the rated movies whose terms of the score
+    (one per liked row, lib.py:51-52 before the ``.mean``) are largest, in that order, with the
+    term and the user's rating. With a ``weighting`` that gives negative weights the terms of
+    disliked movies are negative and rank last. ``explain.explain_topk`` computes them on the
+    GPU for the k returned rows; a row-sharded catalog raises EbertError."""
+    from .explain import explain_topk
+    req = _user_terms(user_id, weighting)
+    if req is None:
+        return []
+    liked, rated, w, ratings = req
+    cat = movies_collab_catalog
+    kw = {}
+    if w is not None:
+        kw["liked_weights"] = [w]
+    if allow is not None:
+        kw["allow"] = _allow_of(allow)
+    scores, rows = score_topk(cat, k, liked=[liked], exclude=[rated], **kw)
+    ex = explain_topk(cat, rows, [liked], liked_weights=[w] if w is not None else None, m=m)
+    s, r = scores[0].cpu().numpy(), rows[0].cpu().numpy()
+    val, pos = ex.contrib[0].cpu().numpy(), ex.pos[0].cpu().numpy()
+    reasons_by_id = {}
+    for j, rr in enumerate(r):
+        if rr < 0:
+            continue
+        reasons_by_id[cat.id_of(int(rr))] = [
+            Reason(tmdb_id=cat.id_of(liked[int(p)]), contribution=float(v),
+                   rating=ratings[int(p)])
+            for v, p in zip(val[j], pos[j]) if p >= 0]
+    return _hydrate_explained(s, r, reasons_by_id)
 
 
 def get_user_recs_batched(batcher, user_id: str, k: int = 10, allow=None,

@@ -33,3 +33,15 @@ class Movie(BaseModel):  # shared/models.py:33-49
 class Recommendation(BaseModel):  # shared/models.py:73-75
     movie: Movie
     score: float
+
+
+class Reason(BaseModel):  # (no counterpart in the reference: one term of lib.py:51-52's mean)
+    tmdb_id: str          # a movie the user rated
+    contribution: float   # its term of the recommendation's score
+    rating: float         # the user's rating of it
+
+
+class ExplainedRecommendation(BaseModel):
+    movie: Movie
+    score: float
+    reasons: List[Reason]
