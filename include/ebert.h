@@ -89,7 +89,10 @@ extern "C" {
  *        (additive; liked_w == NULL launches the kernels of 0.7.0; no workspace size changes).
  * 0.9.0: explanations, the per-liked-row terms of a returned score: ebt_explain_workspace_bytes,
  *        ebt_liked_contrib, ebt_explain_select, ebt_explain_topk (additive; no existing kernel,
- *        struct, signature or workspace size changes). */
+ *        struct, signature or workspace size changes).
+ * 0.10.0: diversified top-k, greedy maximal marginal relevance over a candidate pool:
+ *        ebt_mmr_workspace_bytes, ebt_pool_gram, ebt_mmr_select, ebt_mmr_topk (additive; no
+ *        existing entry, struct, kernel or workspace size changes). */
 int ebt_version(void);
 
 /* Message for the last non-zero return on this thread ("" if none). */
@@ -970,6 +973,61 @@ int ebt_explain_topk(const ebt_catalog* cat, int64_t B, const int64_t* liked_off
                      const int64_t* rows, int32_t k, int32_t m, int largest, void* workspace,
                      size_t ws_bytes, double* out_val, int32_t* out_pos, int64_t* out_row,
                      double* out_total, int32_t* status, void* stream);
+
+/* ---- diversified top-k (0.10.0): greedy maximal marginal relevance over a candidate pool -----
+ * The reference sorts by score and cuts at k (lib.py:51-55), so the k best rows may be near
+ * copies of one another. These entries re-rank a POOL of p > k rows per query: k picks, each
+ * maximising lam * relevance - (1 - lam) * (largest cosine to a row already picked). The cosine
+ * between two catalog rows is lib.py:51's quantity, used among the results. Everything is
+ * float64 and every operation is rounded one at a time.
+ *
+ * Inputs per query b: rows [B][p], GLOBAL rows of ONE unsharded catalog (rows [row_offset,
+ * row_offset + n)), -1 = an empty slot, and rel [B][p], their relevances -- what a search with
+ * k = p returned is the intended input (results of masked and sub-catalog searches are parent
+ * rows and qualify); any list is legal. A slot is a CANDIDATE iff its row is >= 0 and its rel is
+ * not NaN.
+ *
+ * ebt_pool_gram: gram[(b * p + i) * p + j] = S(b, i, j) = (x_i . x_j) / (g_i * g_j), g the
+ * catalog's guarded gnorm64, so a zero-norm row has S = 0 against everything, itself included
+ * (sklearn); NaN where slot i or j is empty. The dot products run on the float64 MFMA in a fixed
+ * order that depends on d and the dtype only (csrc/diversify.hip, the rule of csrc/explain.hip):
+ * query b's matrix has the same bits alone or in any batch, S(b, i, j) and S(b, j, i) have the
+ * same bits, and permuting the pool permutes the matrix bitwise. A pool row outside the catalog
+ * is never read: status[b] = -2 and every value of that query is NaN; otherwise status[b] = 1
+ * (device int32 [B]; nothing is read back, the call only enqueues).
+ *
+ * ebt_mmr_select, with oml = 1.0 - lam computed once:
+ *   pen_i = +0.0 for every i
+ *   for t = 0 .. k-1:
+ *     v_i = (lam * rel_i) - (oml * pen_i)         over the candidates not yet picked
+ *     s   = arg max by (v desc, position asc)     (-0 equals +0; a NaN v is never picked)
+ *     out_pos[b][t] = s; out_rows[b][t] = rows[b][s]; out_rel[b][t] = rel_s (the input's bits);
+ *     out_mmr[b][t] = v_s
+ *     pen_i = S(b, s, i) if t == 0, else S(b, s, i) > pen_i ? S(b, s, i) : pen_i
+ * Slots past the candidates read -1 / -1 / NaN / NaN. With lam == 1 the result is the candidates
+ * ordered by (rel desc, position asc): for a search result its own first k, bit for bit.
+ * 1 <= k <= p <= EBT_MMR_POOL_MAX; lam is a host double in [0, 1]. status may be NULL; a query
+ * with status[b] < 0 gets all-empty outputs.
+ *
+ * ebt_mmr_topk: the two above over a caller's workspace of ebt_mmr_workspace_bytes(B, p) bytes
+ * (the matrices: 8 * B * p * p rounded up to 256, at least 256; 0 for B < 1, p < 1,
+ * p > EBT_MMR_POOL_MAX or a product that overflows).
+ *
+ * Found on the host before any GPU call, EBT_EINVAL with a message that starts with the entry's
+ * name: a null pointer, p or k out of range, lam outside [0, 1] or NaN, a catalog whose ld < d,
+ * a workspace that is too small. No timer stage is recorded. */
+#define EBT_MMR_POOL_MAX 512
+size_t ebt_mmr_workspace_bytes(int64_t B, int32_t p);
+int ebt_pool_gram(const ebt_catalog* cat, int64_t B, const int64_t* rows, int32_t p,
+                  double* gram, int32_t* status, void* stream);
+int ebt_mmr_select(const double* gram, const double* rel, const int64_t* rows, int64_t B,
+                   int32_t p, int32_t k, double lam, const int32_t* status,
+                   int32_t* out_pos, int64_t* out_rows, double* out_rel, double* out_mmr,
+                   void* stream);
+int ebt_mmr_topk(const ebt_catalog* cat, int64_t B, const double* rel, const int64_t* rows,
+                 int32_t p, int32_t k, double lam, void* workspace, size_t ws_bytes,
+                 int32_t* out_pos, int64_t* out_rows, double* out_rel, double* out_mmr,
+                 int32_t* status, void* stream);
 
 /* ---- two-phase top-k over a row-sharded catalog (robot_ebert_amd/distributed.py) ---------
  * Phase 1, every rank: ebt_cosine_screen = ebt_cosine_topk_prepared without the rescore: the shard's k'

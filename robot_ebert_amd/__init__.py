@@ -22,6 +22,10 @@ unweighted call has; ``lib.get_user_recs(..., weighting=)`` maps a user's rating
 
 ``explain_topk`` (ABI 0.9.0) says why: for the rows a search returned, the per-liked-row terms of
 each score and the m largest of them; ``lib.get_user_recs_explained`` attaches them as reasons.
+
+``diversify_topk`` (ABI 0.10.0) trades relevance for variety: from a pool of the p best rows it
+picks k greedily by maximal marginal relevance, lam * score - (1 - lam) * (largest cosine to a
+row already picked); ``lib.get_user_recs_diverse`` is the recommend call over it.
 """
 from ._lib import EbertError, Timer, load  # noqa: F401
 from .catalog import Catalog  # noqa: F401
@@ -29,6 +33,7 @@ from .allow import AllowMasks, SubCatalog  # noqa: F401
 from .search import (merge_topk, prepare_queries, rescore_rows, score_topk,  # noqa: F401
                      score_topk_finish, score_topk_submit)
 from .explain import Explanation, explain_topk  # noqa: F401
+from .diversify import Diversified, diversify_topk  # noqa: F401
 from . import ops  # noqa: F401,E402  (registers torch.ops.ebert.*)
 
 __version__ = "0.1.0"

@@ -27,6 +27,7 @@ EBT_FLAG_THETA = 4
 EBT_FLAG_LIKED_CHECKED = 8   # ebert.h: the liked CSR was checked on the host (no read-back)
 EBT_FILTER_SLOTS_MAX = 128
 EBT_EXPLAIN_M_MAX = 64       # ebert.h: the most reasons ebt_explain_select returns per row
+EBT_MMR_POOL_MAX = 512       # ebert.h: the largest candidate pool of ebt_pool_gram / ebt_mmr_*
 
 
 class EbertError(RuntimeError):
@@ -148,6 +149,12 @@ _SIGNATURES = {
                            _INT),
     "ebt_explain_topk": ([_PCAT, _I64, _VP, _VP, _VP, _I64, _VP, _I32, _I32, _INT, _VP, _SZ,
                           _VP, _VP, _VP, _VP, _VP, _VP], _INT),
+    "ebt_mmr_workspace_bytes": ([_I64, _I32], _SZ),
+    "ebt_pool_gram": ([_PCAT, _I64, _VP, _I32, _VP, _VP, _VP], _INT),
+    "ebt_mmr_select": ([_VP, _VP, _VP, _I64, _I32, _I32, ctypes.c_double, _VP, _VP, _VP, _VP,
+                        _VP, _VP], _INT),
+    "ebt_mmr_topk": ([_PCAT, _I64, _VP, _VP, _I32, _I32, ctypes.c_double, _VP, _SZ, _VP, _VP,
+                      _VP, _VP, _VP, _VP], _INT),
     "ebt_sharded_workspace_bytes": ([_PCAT, _PCOMM, _I64, _I32, _POPT], _SZ),
     "ebt_cosine_topk_sharded": ([_PCAT, _PCOMM, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP,
                                  _POPT, _VP, _SZ, _VP, _VP, _VP, _VP], _INT),

@@ -11,9 +11,9 @@ reference's other routers (movies, search, login) are out of scope.
 """
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
-from fastapi import APIRouter, FastAPI
+from fastapi import APIRouter, FastAPI, Query
 
 from . import lib
 from .models import ExplainedRecommendation, Recommendation
@@ -39,6 +39,17 @@ def get_user_recommendations_explained(user_id: str, k: int = 10,
     """the same recommendations, each with the m rated movies that contributed most to its score
     (no counterpart in the reference; never batched)"""
     return lib.get_user_recs_explained(user_id=user_id, k=k, m=m)
+
+
+@router.get("/users/{user_id}/recommendations/diverse/")
+def get_user_recommendations_diverse(user_id: str, k: int = 10,
+                                     lam: float = Query(0.7, ge=0.0, le=1.0),
+                                     pool: Optional[int] = Query(None, ge=1, le=512)
+                                     ) -> List[Recommendation]:
+    """k recommendations picked from the pool best by maximal marginal relevance, in selection
+    order: lam = 1 is the plain top k, smaller values trade relevance for variety (no
+    counterpart in the reference; never batched)"""
+    return lib.get_user_recs_diverse(user_id=user_id, k=k, lam=lam, pool=pool)
 
 
 def app(batcher=None) -> FastAPI:

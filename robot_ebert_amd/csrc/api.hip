@@ -626,7 +626,7 @@ using namespace ebt;
 
 extern "C" {
 
-int ebt_version(void) { return 900; }  // 0.9.0: explanations, per-liked-row contributions (ebert.h)
+int ebt_version(void) { return 1000; }  // 0.10.0: diversified top-k, greedy MMR over a pool (ebert.h)
 
 const char* ebt_last_error(void) { return g_err; }
 

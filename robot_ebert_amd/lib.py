@@ -293,6 +293,43 @@ def get_user_recs_explained(user_id: str, k: int = 10, m: int = 3,
     return _hydrate_explained(s, r, reasons_by_id)
 
 
+def get_user_recs_diverse(user_id: str, k: int = 10, lam: float = 0.7,
+                          pool: Optional[int] = None,
+                          weighting: Optional[Callable[[float], float]] = None
+                          ) -> List[Recommendation]:
+    """``get_user_recs`` with variety: the same SQL, liked / rated sets and errors (``[]`` for a
+    user without ratings, sklearn's ValueError for one without a liked movie), but the k movies
+    are picked from the ``pool`` best (default min(10 k, 512, catalog rows)) greedily by maximal
+    marginal relevance, each pick maximising lam * score - (1 - lam) * (largest cosine to a movie
+    already picked) (``diversify.diversify_topk``; lam = 1 is the plain top k).
+
+    Returns ``Recommendation(movie, score)`` with the relevance as the score, in SELECTION order.
+    Movies are paired with their scores by tmdb_id; one that ``movies`` lacks is dropped (there is
+    no reference order to mimic here, so lib.py:58-62's zip -- SURVEY a-8 -- is not reproduced).
+    A row-sharded catalog raises EbertError."""
+    from . import diversify
+    from ._lib import EBT_MMR_POOL_MAX
+    from .diversify import diversify_topk
+    diversify._check_lam(lam)
+    if pool is not None:
+        diversify._check_pool(pool)
+    req = _user_terms(user_id, weighting)
+    if req is None:
+        return []
+    liked, rated, w, _ = req
+    cat = movies_collab_catalog
+    if pool is None:
+        pool = min(10 * k, EBT_MMR_POOL_MAX, cat.n)
+    kw = {"liked_weights": [w]} if w is not None else {}
+    scores, rows = score_topk(cat, pool, liked=[liked], exclude=[rated], **kw)
+    picked = diversify_topk(cat, scores, rows, min(k, int(rows.shape[1])), lam=lam)
+    pairs = [(cat.id_of(int(rr)), float(ss))
+             for ss, rr in zip(picked.scores[0].cpu().numpy(), picked.rows[0].cpu().numpy())
+             if rr >= 0]
+    movies = {m.tmdb_id: m for m in get_movies(tmdb_ids=sorted(t for t, _ in pairs))}
+    return [Recommendation(movie=movies[t], score=sc) for t, sc in pairs if t in movies]
+
+
 def get_user_recs_batched(batcher, user_id: str, k: int = 10, allow=None,
                           weighting: Optional[Callable[[float], float]] = None
                           ) -> List[Recommendation]:
