@@ -97,6 +97,17 @@ __device__ __forceinline__ float key2f(uint32_t k) {
   uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
   return __uint_as_float(u);
 }
+// float64: 0 = NaN only (-inf has a key); -0 and +0 are one value
+__device__ __forceinline__ uint64_t f64_key(double x) {
+  if (!(x == x)) return 0ull;  // NaN -> below -inf
+  uint64_t u = (uint64_t)__double_as_longlong(x);
+  if (x == 0.0) u = 0ull;      // -0 == +0
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_f64(uint64_t k) {
+  const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __longlong_as_double((long long)u);
+}
 
 // Workgroup barrier for LDS traffic only. __syncthreads() also waits for the wave's outstanding
 // GLOBAL loads (its release fence is s_waitcnt vmcnt(0)), which empties a register prefetch
@@ -256,6 +267,14 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_max_u32(v), 63);
 }
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return ~wave_max_u32(~v); }
+// wave-wide max of 64-bit keys (uniform). The wave arg-best by (key descending, position
+// ascending) of each lane's candidate (bk, bp) is best = wave_max_u64(bk), then, unless best is 0
+// (no lane has a candidate), wave_min_u32(bk == best ? bp : 0xFFFFFFFFu).
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t bk) {
+  const uint32_t hi = wave_max_u32((uint32_t)(bk >> 32));
+  const uint32_t lo = wave_max_u32((uint32_t)(bk >> 32) == hi ? (uint32_t)bk : 0u);
+  return ((uint64_t)hi << 32) | lo;
+}
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 

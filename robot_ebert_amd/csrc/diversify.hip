@@ -23,17 +23,12 @@
 //                        one read of row s of the matrix.
 //
 // Arithmetic order (the matrix is compared bitwise across launches, batches and permutations of
-// the pool): explain.hip's rule. The dot product of a pair of rows is accumulated by the MFMAs of
-// one wave in a fixed order -- K slabs ascending; inside a slab two groups of four 16-byte
-// chunks; inside a group the element s of each chunk, s ascending, one MFMA per s whose four K
-// values are element s of the group's four chunks (lane >> 4 picks the chunk). Both operands
-// permute alike and products commute, so dot(i, j) and dot(j, i) have the same bits, and the
-// order depends on d and the dtype only -- not on p, the tile a slot lands in, or which other
-// queries share the batch. Columns past d are staged as zeros. The element path (rows that are
-// not 16-byte aligned, d = 77) stages the same values into the same LDS positions, so it gives
-// the chunk path's bits. Then, rounded one operation at a time (no contraction): g = g_i * g_j,
-// S = dot / g; and in the selection v = (lam * rel) - ((1 - lam) * pen).
-#include "common.h"
+// the pool): the dot product follows the rule at the top of pair_f64.h, under which dot(i, j)
+// and dot(j, i) have the same bits and the order depends on d and the dtype only -- not on p,
+// the tile a slot lands in, or which other queries share the batch. Then, rounded one operation
+// at a time (no contraction): g = g_i * g_j, S = dot / g; and in the selection
+// v = (lam * rel) - ((1 - lam) * pen).
+#include "pair_f64.h"
 
 namespace ebt {
 
@@ -42,25 +37,14 @@ namespace {
 constexpr int DV_THREADS = 512;
 constexpr int DV_BT = 128;                  // slots per side of a workgroup tile (8 MFMA tiles)
 constexpr int DV_ROWS = 2 * DV_BT;          // staged rows: the A panel, then the B panel
-constexpr int DV_SLAB = 128;                // bytes of every staged row per K slab
-constexpr int DV_LDR = DV_SLAB + 16;        // LDS row stride: the 16 rows of a b128 read land in
-                                            // 64 distinct banks (36 words apart)
-constexpr int DV_CPR = DV_SLAB / 16;        // 16-byte chunks per row and slab
-constexpr int DV_CPT = DV_ROWS * DV_CPR / DV_THREADS;   // chunks a thread stages per slab
 constexpr int DV_WM = 4, DV_WN = 2;         // 16 x 16 tiles per wave (the waves are 2 x 4)
-static_assert(DV_ROWS * DV_CPR % DV_THREADS == 0 && DV_CPT % 2 == 0, "staging");
 static_assert(DV_BT == 2 * 16 * DV_WM && DV_BT == 4 * 16 * DV_WN, "wave tiles");
+typedef PairTile<DV_THREADS, DV_ROWS, DV_WM, DV_WN> DvTile;
+static_assert(DvTile::CPT % 2 == 0, "a diagonal tile stages half");
 constexpr int MMR_SLOTS = EBT_MMR_POOL_MAX / 64;   // pool slots a lane of the selection holds
 
-typedef double f64x4_t __attribute__((ext_vector_type(4)));
-
 struct GramArgs {
-  const void* data;        // the catalog's matrix [n][ld]
-  int64_t ld;
-  int d;
-  int vec;                 // rows are 16-byte aligned (base and row stride)
-  const double* gnorm;
-  int64_t row_offset, n;
+  RowSrc src;
   int64_t B;
   const int64_t* rows;     // [B][p] GLOBAL pool rows, -1 = empty
   int p;
@@ -71,10 +55,8 @@ struct GramArgs {
 // LDS bytes of one staged K slab: a pool of one tile (p <= DV_BT) has diagonal tiles only, which
 // stage a single panel. The kernel holds two slabs.
 __host__ __device__ inline int gram_slab_bytes(int p) {
-  return (p <= DV_BT ? DV_BT : DV_ROWS) * DV_LDR;
+  return (p <= DV_BT ? DV_BT : DV_ROWS) * DvTile::LDR;
 }
-
-__device__ __forceinline__ double dv_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // One operation at a time, so that the result does not depend on what the compiler would fuse
 __device__ __forceinline__ double cos_term(double dot, double gi, double gj) {
@@ -89,80 +71,10 @@ __device__ __forceinline__ double mmr_value(double lam, double oml, double rel, 
   return a - c;
 }
 
-// elements e0 .. e0 + 16 / sizeof(U) of local row r as one 16-byte chunk; zeros past d and for
-// r < 0 (a row that is not staged). The element form reads only elements below d.
-template <typename U>
-__device__ __forceinline__ uint4 load_chunk(const GramArgs& a, int64_t r, int e0) {
-  constexpr int PER = 16 / (int)sizeof(U);
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (r < 0 || e0 >= a.d) return v;
-  const U* p = (const U*)a.data + (r * a.ld + e0);
-  if (a.vec && e0 + PER <= a.d) return *(const uint4*)p;
-  U t[PER];
-#pragma unroll
-  for (int e = 0; e < PER; ++e) t[e] = e0 + e < a.d ? p[e] : (U)0;
-  __builtin_memcpy(&v, t, 16);
-  return v;
-}
-
-// element s of a staged 16-byte chunk as float64
-template <int DT, int S>
-__device__ __forceinline__ double chunk_elem(const uint4& v) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  if constexpr (DT == EBT_F32) {
-    return (double)__uint_as_float(w[S]);
-  } else if constexpr (DT == EBT_F64) {
-    return f64_from_halves(w[2 * S], w[2 * S + 1]);
-  } else {
-    const uint16_t h = (uint16_t)(w[S >> 1] >> (16 * (S & 1)));
-    if constexpr (DT == EBT_BF16) return bf16_bits_to_f64(h);
-    else return f16_bits_to_f64(h);
-  }
-}
-
-template <int DT> struct DvElem { typedef uint32_t U; };
-template <> struct DvElem<EBT_F64> { typedef uint64_t U; };
-template <> struct DvElem<EBT_BF16> { typedef uint16_t U; };
-template <> struct DvElem<EBT_F16> { typedef uint16_t U; };
-
-// MFMA step S of one group of four chunks: lane l supplies element S of chunk (l >> 4) of row
-// (l & 15) of each tile as its A (slots i) or B (slots j) operand
-// `live` has bit t * DV_WN + u set for the tiles this wave computes (wave-uniform)
-template <int DT, int S>
-__device__ __forceinline__ void mfma_step(const uint4 (&ra)[DV_WM], const uint4 (&rb)[DV_WN],
-                                          uint32_t live, f64x4_t (&acc)[DV_WM][DV_WN]) {
-  double fa[DV_WM], fb[DV_WN];
-#pragma unroll
-  for (int t = 0; t < DV_WM; ++t) fa[t] = chunk_elem<DT, S>(ra[t]);
-#pragma unroll
-  for (int u = 0; u < DV_WN; ++u) fb[u] = chunk_elem<DT, S>(rb[u]);
-#pragma unroll
-  for (int t = 0; t < DV_WM; ++t)
-#pragma unroll
-    for (int u = 0; u < DV_WN; ++u)
-      if ((live >> (t * DV_WN + u)) & 1u)
-        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[t], fb[u], acc[t][u], 0, 0, 0);
-}
-
-template <int DT, int S, int PER>
-struct MfmaSteps {
-  __device__ __forceinline__ static void run(const uint4 (&ra)[DV_WM], const uint4 (&rb)[DV_WN],
-                                             uint32_t live, f64x4_t (&acc)[DV_WM][DV_WN]) {
-    mfma_step<DT, S>(ra, rb, live, acc);
-    MfmaSteps<DT, S + 1, PER>::run(ra, rb, live, acc);
-  }
-};
-template <int DT, int PER>
-struct MfmaSteps<DT, PER, PER> {
-  __device__ __forceinline__ static void run(const uint4 (&)[DV_WM], const uint4 (&)[DV_WN],
-                                             uint32_t, f64x4_t (&)[DV_WM][DV_WN]) {}
-};
-
 template <int DT>
 __global__ __launch_bounds__(DV_THREADS) void pool_gram_kernel(const GramArgs a) {
-  typedef typename DvElem<DT>::U U;
-  constexpr int PER = 16 / (int)sizeof(U);       // elements per 16-byte chunk
-  constexpr int KE = DV_SLAB / (int)sizeof(U);   // elements per slab
+  typedef typename PairElem<DT>::U U;
+  constexpr int KE = DvTile::ke<DT>();           // elements per slab
   extern __shared__ __attribute__((aligned(16))) unsigned char tile[];   // slabs s, s + 1
   __shared__ int64_t s_row[DV_ROWS];   // local catalog row of a staged row, -1: none (zeros)
   __shared__ double s_g[DV_ROWS];
@@ -172,7 +84,7 @@ __global__ __launch_bounds__(DV_THREADS) void pool_gram_kernel(const GramArgs a)
   const int p = a.p;
   const int64_t T = (p + DV_BT - 1) / DV_BT;     // tiles per side of a query's matrix
   const int TILE = gram_slab_bytes(p);           // bytes of one staged slab
-  const int nslabs = (a.d + KE - 1) / KE;
+  const int nslabs = (a.src.d + KE - 1) / KE;
   for (int64_t blk = blockIdx.x; blk < a.B * T * T; blk += gridDim.x) {
     const int64_t b = blk / (T * T);
     const int mb = (int)((blk % (T * T)) / T), nb = (int)(blk % T);
@@ -181,105 +93,57 @@ __global__ __launch_bounds__(DV_THREADS) void pool_gram_kernel(const GramArgs a)
     const int nrows = p - n0 < DV_BT ? p - n0 : DV_BT;
     const bool diag = mb == nb;        // one panel serves as both operands
     const int bbase = diag ? 0 : DV_BT;
-    const int nstage = diag ? DV_CPT / 2 : DV_CPT;
+    const int nstage = diag ? DvTile::CPT / 2 : DvTile::CPT;
     const int64_t* __restrict__ pool = a.rows + b * p;
     double* __restrict__ outb = a.gram + b * p * p;
     // ---- the query's rows are checked before any of them is followed --------------------------
-    __syncthreads();
-    if (tid == 0) s_bad = 0;
-    __syncthreads();
-    bool bad = false;
-    for (int j = tid; j < p; j += DV_THREADS) {
-      const int64_t g = pool[j];
-      const int64_t r = g - a.row_offset;
-      bad |= g != -1 && (r < 0 || r >= a.n);
-    }
-    if (bad) s_bad = 1;
-    __syncthreads();
-    const bool qbad = s_bad != 0;
+    const bool qbad = block_any(rows_outside<DV_THREADS>(a.src, pool, p, true), &s_bad);
     if (mb == 0 && nb == 0 && tid == 0) a.status[b] = qbad ? -2 : 1;
     if (qbad) {   // nothing of this query is read: its values are NaN
       for (int t = tid; t < mrows * nrows; t += DV_THREADS)
-        outb[(int64_t)(m0 + t / nrows) * p + n0 + t % nrows] = dv_nan();
+        outb[(int64_t)(m0 + t / nrows) * p + n0 + t % nrows] = f64_nan();
       continue;
     }
     for (int i = tid; i < DV_ROWS; i += DV_THREADS) {
       const int slot = i < DV_BT ? (i < mrows ? m0 + i : -1)
                                  : (!diag && i - DV_BT < nrows ? n0 + i - DV_BT : -1);
       int64_t r = -1;
-      if (slot >= 0 && pool[slot] != -1) r = pool[slot] - a.row_offset;
+      if (slot >= 0 && pool[slot] != -1) r = pool[slot] - a.src.row_offset;
       s_row[i] = r;
-      s_g[i] = r >= 0 ? a.gnorm[r] : 1.0;
+      s_g[i] = r >= 0 ? a.src.gnorm[r] : 1.0;
     }
     __syncthreads();
-    const int nta_all = (mrows - wm * 16 * DV_WM + 15) / 16;
-    const int nta = nta_all < 0 ? 0 : (nta_all > DV_WM ? DV_WM : nta_all);
-    const int ntb_all = (nrows - wn * 16 * DV_WN + 15) / 16;
-    const int ntb = ntb_all < 0 ? 0 : (ntb_all > DV_WN ? DV_WN : ntb_all);
+    const int nta = DvTile::tiles(mrows, wm * 16 * DV_WM, DV_WM);
+    const int ntb = DvTile::tiles(nrows, wn * 16 * DV_WN, DV_WN);
     // The tiles this wave computes: those that reach into the pool and, on a diagonal workgroup
     // tile, only those on or above the diagonal -- S(j, i) is S(i, j)'s bits (products commute),
     // so the epilogue writes a tile above the diagonal to both places
-    uint32_t live = 0u;
+    uint32_t live = DvTile::live_mask(nta, ntb);
+    if (diag) {
 #pragma unroll
-    for (int t = 0; t < DV_WM; ++t)
+      for (int t = 0; t < DV_WM; ++t)
 #pragma unroll
-      for (int u = 0; u < DV_WN; ++u)
-        if (t < nta && u < ntb && (!diag || wm * DV_WM + t <= wn * DV_WN + u))
-          live |= 1u << (t * DV_WN + u);
+        for (int u = 0; u < DV_WN; ++u)
+          if (wm * DV_WM + t > wn * DV_WN + u) live &= ~(1u << (t * DV_WN + u));
+    }
     f64x4_t acc[DV_WM][DV_WN];
-#pragma unroll
-    for (int t = 0; t < DV_WM; ++t)
-#pragma unroll
-      for (int u = 0; u < DV_WN; ++u) acc[t][u] = f64x4_t{0.0, 0.0, 0.0, 0.0};
+    DvTile::clear(acc);
     // Slab s + 1 travels from memory into registers while the MFMAs of slab s run, and goes into
     // the other half of `tile` after them: one barrier per slab. (The barrier that ended slab
     // s - 1 is what makes that half free: every wave has read it.)
-    uint4 pre[DV_CPT];
-#pragma unroll
-    for (int i = 0; i < DV_CPT; ++i) {
-      const int id = tid + DV_THREADS * i;
-      if (i < nstage) {
-        pre[i] = load_chunk<U>(a, s_row[id / DV_CPR], (id % DV_CPR) * PER);
-        *(uint4*)(tile + (id / DV_CPR) * DV_LDR + (id % DV_CPR) * 16) = pre[i];
-      }
-    }
+    uint4 pre[DvTile::CPT];
+    DvTile::fetch<U>(a.src, s_row, 0, nstage, pre);
+    DvTile::store(tile, nstage, pre);
     __syncthreads();
     for (int s = 0; s < nslabs; ++s) {
-      const unsigned char* cur = tile + (s & 1) * TILE;
-      unsigned char* nxt = tile + ((s + 1) & 1) * TILE;
-      if (s + 1 < nslabs) {
-#pragma unroll
-        for (int i = 0; i < DV_CPT; ++i) {
-          const int id = tid + DV_THREADS * i;
-          if (i < nstage)
-            pre[i] = load_chunk<U>(a, s_row[id / DV_CPR], (s + 1) * KE + (id % DV_CPR) * PER);
-        }
-      }
-      if (live) {   // (wave-uniform)
-#pragma unroll
-        for (int c = 0; c < DV_CPR / 4; ++c) {
-          if (s * KE + c * 4 * PER >= a.d) break;   // a group of chunks wholly past d: zeros
-          uint4 ra[DV_WM], rb[DV_WN];
-          const int at = (lane & 15) * DV_LDR + c * 64 + (lane >> 4) * 16;
-#pragma unroll
-          for (int t = 0; t < DV_WM; ++t)
-            ra[t] = *(const uint4*)(cur + (wm * 16 * DV_WM + t * 16) * DV_LDR + at);
-#pragma unroll
-          for (int u = 0; u < DV_WN; ++u)
-            rb[u] = *(const uint4*)(cur + (bbase + wn * 16 * DV_WN + u * 16) * DV_LDR + at);
-          MfmaSteps<DT, 0, PER>::run(ra, rb, live, acc);
-        }
-      }
-      if (s + 1 < nslabs) {
-#pragma unroll
-        for (int i = 0; i < DV_CPT; ++i) {
-          const int id = tid + DV_THREADS * i;
-          if (i < nstage) *(uint4*)(nxt + (id / DV_CPR) * DV_LDR + (id % DV_CPR) * 16) = pre[i];
-        }
-      }
+      if (s + 1 < nslabs) DvTile::fetch<U>(a.src, s_row, (s + 1) * KE, nstage, pre);
+      if (live)   // (wave-uniform)
+        DvTile::mma<DT>(tile + (s & 1) * TILE, wm * 16 * DV_WM, bbase + wn * 16 * DV_WN, lane, s,
+                        a.src.d, live, acc);
+      if (s + 1 < nslabs) DvTile::store(tile + ((s + 1) & 1) * TILE, nstage, pre);
       __syncthreads();
     }
-    // C/D of v_mfma_f64_16x16x4_f64: column = lane & 15, row = (lane >> 4) + 4 * register
+    // C/D of v_mfma_f64_16x16x4_f64 (pair_f64.h): column = lane & 15, row = (lane >> 4) + 4 * i
 #pragma unroll
     for (int t = 0; t < DV_WM; ++t) {
 #pragma unroll
@@ -292,7 +156,7 @@ __global__ __launch_bounds__(DV_THREADS) void pool_gram_kernel(const GramArgs a)
           const int ii = wm * 16 * DV_WM + t * 16 + (lane >> 4) + 4 * i;
           if (ii < mrows && jj < nrows) {
             const double v = s_row[ii] < 0 || s_row[bbase + jj] < 0
-                                 ? dv_nan()
+                                 ? f64_nan()
                                  : cos_term(acc[t][u][i], s_g[ii], s_g[bbase + jj]);
             outb[(int64_t)(m0 + ii) * p + n0 + jj] = v;
             if (mirror) outb[(int64_t)(m0 + jj) * p + n0 + ii] = v;   // (m0 == n0 here)
@@ -318,14 +182,6 @@ struct MmrArgs {
   double* mmr;
 };
 
-// Order-preserving key of a value, larger = better; 0 = NaN (never selected). -0 and +0 are one
-// value.
-__device__ __forceinline__ uint64_t mmr_key(double v) {
-  if (!(v == v)) return 0ull;
-  const uint64_t u = v == 0.0 ? 0ull : (uint64_t)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
 __global__ __launch_bounds__(256) void mmr_select_kernel(const MmrArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int p = a.p, k = a.k;
@@ -337,7 +193,7 @@ __global__ __launch_bounds__(256) void mmr_select_kernel(const MmrArgs a) {
 #pragma unroll
     for (int c = 0; c < MMR_SLOTS; ++c) {
       const int i = lane + 64 * c;
-      rel[c] = dv_nan();
+      rel[c] = f64_nan();
       pen[c] = 0.0;
       if (good && i < p) {
         rel[c] = a.rel[b * p + i];
@@ -352,7 +208,7 @@ __global__ __launch_bounds__(256) void mmr_select_kernel(const MmrArgs a) {
 #pragma unroll
       for (int c = 0; c < MMR_SLOTS; ++c) {   // positions ascend with c: > keeps the first
         const double v = mmr_value(a.lam, a.oml, rel[c], pen[c]);
-        const uint64_t key = ((alive >> c) & 1u) ? mmr_key(v) : 0ull;
+        const uint64_t key = ((alive >> c) & 1u) ? f64_key(v) : 0ull;
         if (key > bk) {
           bk = key;
           bp = (uint32_t)(lane + 64 * c);
@@ -360,9 +216,7 @@ __global__ __launch_bounds__(256) void mmr_select_kernel(const MmrArgs a) {
           br = rel[c];
         }
       }
-      const uint32_t hi = wave_max_u32((uint32_t)(bk >> 32));
-      const uint32_t lo = wave_max_u32((uint32_t)(bk >> 32) == hi ? (uint32_t)bk : 0u);
-      const uint64_t best = ((uint64_t)hi << 32) | lo;
+      const uint64_t best = wave_max_u64(bk);
       if (best == 0ull) break;   // nothing left (wave-uniform)
       const uint32_t s = wave_min_u32(bk == best ? bp : 0xFFFFFFFFu);
       if (bp == s) {             // the one lane that holds slot s
@@ -385,25 +239,10 @@ __global__ __launch_bounds__(256) void mmr_select_kernel(const MmrArgs a) {
     for (int tt = t + lane; tt < k; tt += 64) {
       a.pos[b * k + tt] = -1;
       a.row[b * k + tt] = -1;
-      a.orel[b * k + tt] = dv_nan();
-      a.mmr[b * k + tt] = dv_nan();
+      a.orel[b * k + tt] = f64_nan();
+      a.mmr[b * k + tt] = f64_nan();
     }
   }
-}
-
-int64_t grid_of(int64_t items, int64_t cap) { return items < 1 ? 1 : (items > cap ? cap : items); }
-
-int check_catalog(const char* who, const ebt_catalog* cat) {
-  if (!cat || !cat->data || !cat->gnorm64) {
-    set_error("%s: null pointer", who);
-    return EBT_EINVAL;
-  }
-  if (cat->n < 1 || cat->d < 1 || cat->ld < cat->d || cat->dtype < 0 || cat->dtype > 3) {
-    set_error("%s: bad catalog (n=%lld d=%d ld=%lld dtype=%d)", who, (long long)cat->n, cat->d,
-              (long long)cat->ld, cat->dtype);
-    return EBT_EINVAL;
-  }
-  return EBT_OK;
 }
 
 int check_pool(const char* who, int64_t B, int32_t p) {
@@ -454,26 +293,17 @@ int ebt_pool_gram(const ebt_catalog* cat, int64_t B, const int64_t* rows, int32_
   rc = check_pool(who, B, p);
   if (rc) return rc;
   if (B == 0) return EBT_OK;
-  const int es = cat->dtype == EBT_F64 ? 8 : (cat->dtype == EBT_F32 ? 4 : 2);
   GramArgs a;
-  a.data = cat->data; a.ld = cat->ld; a.d = cat->d;
-  a.vec = ((uintptr_t)cat->data & 15) == 0 && (cat->ld * es) % 16 == 0;
-  a.gnorm = cat->gnorm64; a.row_offset = cat->row_offset; a.n = cat->n;
+  a.src = row_src(*cat);
   a.B = B; a.rows = rows; a.p = p; a.gram = gram; a.status = status;
   const int64_t T = ceil_div(p, DV_BT);
   const dim3 grid((unsigned)grid_of(B * T * T, 1 << 20)), block(DV_THREADS);
   hipStream_t st = (hipStream_t)stream;
   const int lds = 2 * gram_slab_bytes(p);
-#define EBT_GRAM_LAUNCH(DT)                                                    \
-  set_max_lds((const void*)pool_gram_kernel<DT>, lds);                         \
-  hipLaunchKernelGGL(pool_gram_kernel<DT>, grid, block, lds, st, a)
-  switch (cat->dtype) {
-    case EBT_F32: EBT_GRAM_LAUNCH(EBT_F32); break;
-    case EBT_BF16: EBT_GRAM_LAUNCH(EBT_BF16); break;
-    case EBT_F16: EBT_GRAM_LAUNCH(EBT_F16); break;
-    default: EBT_GRAM_LAUNCH(EBT_F64); break;
-  }
-#undef EBT_GRAM_LAUNCH
+  for_dtype(cat->dtype, [&](auto dt) {
+    set_max_lds((const void*)pool_gram_kernel<decltype(dt)::value>, lds);
+    hipLaunchKernelGGL(pool_gram_kernel<decltype(dt)::value>, grid, block, lds, st, a);
+  });
   return launch_check("pool_gram_kernel");
 }
 

@@ -17,17 +17,12 @@
 //                        rounds of a wave-wide arg-max over order-preserving 64-bit keys.
 //
 // Arithmetic order (results are compared bitwise across launches, batches and weight scalings):
-// the dot product of a pair of rows is accumulated by the MFMAs of one wave in a fixed order --
-// K slabs ascending; inside a slab two groups of four 16-byte chunks; inside a group the element
-// s of each chunk, s ascending, one MFMA per s whose four K values are element s of the group's
-// four chunks (lane >> 4 picks the chunk). Both operands permute alike, so this is a dot product
-// over all of d in an order that depends on d and the dtype only -- not on k, L_b, the tile a row
-// lands in, or which other queries share the batch. Columns past d are staged as zeros. The
-// element path (rows that are not 16-byte aligned, d = 77) stages the same values into the same
-// LDS positions, so it gives the chunk path's bits. Then, rounded one operation at a time (no
-// contraction): g = g_l * g_j, c = dot / g, t = w_l * c, contrib = t * (1 / W_b), with W_b the
-// sequential sum of |w_l| in CSR order (L_b when there are no weights).
-#include "common.h"
+// the dot product follows the rule at the top of pair_f64.h, which depends on d and the dtype
+// only -- not on k, L_b, the tile a row lands in, or which other queries share the batch. Then,
+// rounded one operation at a time (no contraction): g = g_l * g_j, c = dot / g, t = w_l * c,
+// contrib = t * (1 / W_b), with W_b the sequential sum of |w_l| in CSR order (L_b when there are
+// no weights).
+#include "pair_f64.h"
 
 namespace ebt {
 
@@ -37,24 +32,12 @@ constexpr int EX_THREADS = 256;
 constexpr int EX_BM = 128;                  // result rows per workgroup tile (8 MFMA tiles)
 constexpr int EX_BN = 96;                   // liked rows per workgroup tile (6 MFMA tiles)
 constexpr int EX_ROWS = EX_BM + EX_BN;
-constexpr int EX_SLAB = 128;                // bytes of every staged row per K slab
-constexpr int EX_LDR = EX_SLAB + 16;        // LDS row stride: the 16 rows of a b128 read land in
-                                            // 64 distinct banks (36 words apart)
-constexpr int EX_CPR = EX_SLAB / 16;        // 16-byte chunks per row and slab
-constexpr int EX_CPT = EX_ROWS * EX_CPR / EX_THREADS;   // chunks a thread stages per slab
 constexpr int EX_WM = 4, EX_WN = 3;         // 16 x 16 tiles per wave (the waves are 2 x 2)
-static_assert(EX_ROWS * EX_CPR % EX_THREADS == 0, "staging");
 static_assert(EX_BM == 2 * 16 * EX_WM && EX_BN == 2 * 16 * EX_WN, "wave tiles");
-
-typedef double f64x4_t __attribute__((ext_vector_type(4)));
+typedef PairTile<EX_THREADS, EX_ROWS, EX_WM, EX_WN> ExTile;
 
 struct ExplainArgs {
-  const void* data;        // the catalog's matrix [n][ld]
-  int64_t ld;
-  int d;
-  int vec;                 // rows are 16-byte aligned (base and row stride)
-  const double* gnorm;
-  int64_t row_offset, n;
+  RowSrc src;
   int64_t B;
   const int64_t* off;      // [B + 1] liked CSR
   const int64_t* lrows;    // GLOBAL liked rows
@@ -64,8 +47,6 @@ struct ExplainArgs {
   double* out;             // CSR-shaped [k * nnz]
   int32_t* status;         // [B]
 };
-
-__device__ __forceinline__ double ex_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // One operation at a time, so that the result does not depend on what the compiler would fuse
 __device__ __forceinline__ double contrib_term(double w, double dot, double gl, double gj,
@@ -77,80 +58,11 @@ __device__ __forceinline__ double contrib_term(double w, double dot, double gl, 
   return t * inv_w;
 }
 
-// elements e0 .. e0 + 16 / sizeof(U) of local row r as one 16-byte chunk; zeros past d and for
-// r < 0 (a row that is not staged). The element form reads only elements below d.
-template <typename U>
-__device__ __forceinline__ uint4 load_chunk(const ExplainArgs& a, int64_t r, int e0) {
-  constexpr int PER = 16 / (int)sizeof(U);
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (r < 0 || e0 >= a.d) return v;
-  const U* p = (const U*)a.data + (r * a.ld + e0);
-  if (a.vec && e0 + PER <= a.d) return *(const uint4*)p;
-  U t[PER];
-#pragma unroll
-  for (int e = 0; e < PER; ++e) t[e] = e0 + e < a.d ? p[e] : (U)0;
-  __builtin_memcpy(&v, t, 16);
-  return v;
-}
-
-// element s of a staged 16-byte chunk as float64
-template <int DT, int S>
-__device__ __forceinline__ double chunk_elem(const uint4& v) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  if constexpr (DT == EBT_F32) {
-    return (double)__uint_as_float(w[S]);
-  } else if constexpr (DT == EBT_F64) {
-    return f64_from_halves(w[2 * S], w[2 * S + 1]);
-  } else {
-    const uint16_t h = (uint16_t)(w[S >> 1] >> (16 * (S & 1)));
-    if constexpr (DT == EBT_BF16) return bf16_bits_to_f64(h);
-    else return f16_bits_to_f64(h);
-  }
-}
-
-template <int DT> struct ExElem { typedef uint32_t U; };
-template <> struct ExElem<EBT_F64> { typedef uint64_t U; };
-template <> struct ExElem<EBT_BF16> { typedef uint16_t U; };
-template <> struct ExElem<EBT_F16> { typedef uint16_t U; };
-
-// MFMA step S of one group of four chunks: lane l supplies element S of chunk (l >> 4) of row
-// (l & 15) of each tile as its A (result rows) or B (liked rows) operand
-template <int DT, int S>
-__device__ __forceinline__ void mfma_step(const uint4 (&ra)[EX_WM], const uint4 (&rb)[EX_WN],
-                                          int nta, int ntb, f64x4_t (&acc)[EX_WM][EX_WN]) {
-  double fa[EX_WM], fb[EX_WN];
-#pragma unroll
-  for (int t = 0; t < EX_WM; ++t) fa[t] = chunk_elem<DT, S>(ra[t]);
-#pragma unroll
-  for (int u = 0; u < EX_WN; ++u) fb[u] = chunk_elem<DT, S>(rb[u]);
-#pragma unroll
-  for (int t = 0; t < EX_WM; ++t)
-#pragma unroll
-    for (int u = 0; u < EX_WN; ++u)
-      if (t < nta && u < ntb)   // wave-uniform: tiles past the query's rows are not computed
-        acc[t][u] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[t], fb[u], acc[t][u], 0, 0, 0);
-}
-
-template <int DT, int S, int PER>
-struct MfmaSteps {
-  __device__ __forceinline__ static void run(const uint4 (&ra)[EX_WM], const uint4 (&rb)[EX_WN],
-                                             int nta, int ntb, f64x4_t (&acc)[EX_WM][EX_WN]) {
-    mfma_step<DT, S>(ra, rb, nta, ntb, acc);
-    MfmaSteps<DT, S + 1, PER>::run(ra, rb, nta, ntb, acc);
-  }
-};
-template <int DT, int PER>
-struct MfmaSteps<DT, PER, PER> {
-  __device__ __forceinline__ static void run(const uint4 (&)[EX_WM], const uint4 (&)[EX_WN], int,
-                                             int, f64x4_t (&)[EX_WM][EX_WN]) {}
-};
-
 template <int DT>
 __global__ __launch_bounds__(EX_THREADS, 2) void liked_contrib_kernel(const ExplainArgs a) {
-  typedef typename ExElem<DT>::U U;
-  constexpr int PER = 16 / (int)sizeof(U);       // elements per 16-byte chunk
-  constexpr int KE = EX_SLAB / (int)sizeof(U);   // elements per slab
-  __shared__ __attribute__((aligned(16))) unsigned char tile[EX_ROWS * EX_LDR];
+  typedef typename PairElem<DT>::U U;
+  constexpr int KE = ExTile::ke<DT>();           // elements per slab
+  __shared__ __attribute__((aligned(16))) unsigned char tile[EX_ROWS * ExTile::LDR];
   __shared__ int64_t s_row[EX_ROWS];   // local catalog row of a staged row, -1: none (zeros)
   __shared__ double s_g[EX_ROWS];
   __shared__ double s_w[EX_BN];
@@ -161,7 +73,7 @@ __global__ __launch_bounds__(EX_THREADS, 2) void liked_contrib_kernel(const Expl
   const int wm = wave >> 1, wn = wave & 1;
   const int k = a.k;
   const int64_t mblocks = (k + EX_BM - 1) / EX_BM;
-  const int nslabs = (a.d + KE - 1) / KE;
+  const int nslabs = (a.src.d + KE - 1) / KE;
   for (int64_t blk = blockIdx.x; blk < a.B * mblocks; blk += gridDim.x) {
     const int64_t b = blk / mblocks;
     const int m0 = (int)(blk % mblocks) * EX_BM;
@@ -171,26 +83,13 @@ __global__ __launch_bounds__(EX_THREADS, 2) void liked_contrib_kernel(const Expl
     const int64_t* __restrict__ res = a.rows + b * k;
     double* __restrict__ outb = a.out + (int64_t)k * l0;
     // ---- the query's rows are checked before any of them is followed --------------------------
-    __syncthreads();
-    if (tid == 0) s_bad = 0;
-    __syncthreads();
-    bool bad = false;
-    for (int64_t i = tid; i < Lb; i += EX_THREADS) {
-      const int64_t r = a.lrows[l0 + i] - a.row_offset;
-      bad |= r < 0 || r >= a.n;
-    }
-    for (int j = tid; j < k; j += EX_THREADS) {
-      const int64_t g = res[j];
-      const int64_t r = g - a.row_offset;
-      bad |= g != -1 && (r < 0 || r >= a.n);
-    }
-    if (bad) s_bad = 1;
-    __syncthreads();
-    const bool qbad = s_bad != 0;
+    const bool qbad = block_any(rows_outside<EX_THREADS>(a.src, a.lrows + l0, Lb, false) ||
+                                    rows_outside<EX_THREADS>(a.src, res, k, true),
+                                &s_bad);
     if (m0 == 0 && tid == 0) a.status[b] = qbad ? -2 : 1;
     if (qbad) {   // nothing of this query is read: its outputs are NaN
       for (int64_t t = tid; t < (int64_t)mrows * Lb; t += EX_THREADS)
-        outb[(int64_t)m0 * Lb + t] = ex_nan();
+        outb[(int64_t)m0 * Lb + t] = f64_nan();
       continue;
     }
     // ---- 1 / W_b: the sequential sum of |w_l| in CSR order (thread 0 adds, 256 at a time) ------
@@ -210,80 +109,52 @@ __global__ __launch_bounds__(EX_THREADS, 2) void liked_contrib_kernel(const Expl
       s_inv_w = 1.0 / (double)Lb;
     }
     // ---- the liked rows, EX_BN at a time ------------------------------------------------------
-    const int nta_all = (mrows - wm * 16 * EX_WM + 15) / 16;
-    const int nta = nta_all < 0 ? 0 : (nta_all > EX_WM ? EX_WM : nta_all);
+    const int nta = ExTile::tiles(mrows, wm * 16 * EX_WM, EX_WM);
     for (int64_t n0 = 0; n0 < Lb; n0 += EX_BN) {
       const int nrows = Lb - n0 < EX_BN ? (int)(Lb - n0) : EX_BN;
-      const int ntb_all = (nrows - wn * 16 * EX_WN + 15) / 16;
-      const int ntb = ntb_all < 0 ? 0 : (ntb_all > EX_WN ? EX_WN : ntb_all);
+      // wave-uniform: tiles past the query's rows are not computed
+      const int ntb = ExTile::tiles(nrows, wn * 16 * EX_WN, EX_WN);
+      const uint32_t live = ExTile::live_mask(nta, ntb);
       __syncthreads();   // the epilogue before this one has read the row records
       for (int i = tid; i < EX_ROWS; i += EX_THREADS) {
         int64_t r = -1;
         if (i < EX_BM) {
-          if (i < mrows && res[m0 + i] != -1) r = res[m0 + i] - a.row_offset;
+          if (i < mrows && res[m0 + i] != -1) r = res[m0 + i] - a.src.row_offset;
         } else if (i - EX_BM < nrows) {
-          r = a.lrows[l0 + n0 + (i - EX_BM)] - a.row_offset;
+          r = a.lrows[l0 + n0 + (i - EX_BM)] - a.src.row_offset;
           s_w[i - EX_BM] = a.lw ? a.lw[l0 + n0 + (i - EX_BM)] : 1.0;
         }
         s_row[i] = r;
-        s_g[i] = r >= 0 ? a.gnorm[r] : 1.0;
+        s_g[i] = r >= 0 ? a.src.gnorm[r] : 1.0;
       }
       __syncthreads();
       f64x4_t acc[EX_WM][EX_WN];
-#pragma unroll
-      for (int t = 0; t < EX_WM; ++t)
-#pragma unroll
-        for (int u = 0; u < EX_WN; ++u) acc[t][u] = f64x4_t{0.0, 0.0, 0.0, 0.0};
+      ExTile::clear(acc);
       // slab s + 1 travels from memory into registers while the MFMAs of slab s run
-      uint4 pre[EX_CPT];
-#pragma unroll
-      for (int i = 0; i < EX_CPT; ++i) {
-        const int id = tid + EX_THREADS * i;
-        pre[i] = load_chunk<U>(a, s_row[id / EX_CPR], (id % EX_CPR) * PER);
-      }
+      uint4 pre[ExTile::CPT];
+      ExTile::fetch<U>(a.src, s_row, 0, ExTile::CPT, pre);
       for (int s = 0; s < nslabs; ++s) {
         __syncthreads();   // every wave has read slab s - 1
-#pragma unroll
-        for (int i = 0; i < EX_CPT; ++i) {
-          const int id = tid + EX_THREADS * i;
-          *(uint4*)(tile + (id / EX_CPR) * EX_LDR + (id % EX_CPR) * 16) = pre[i];
-        }
+        ExTile::store(tile, ExTile::CPT, pre);
         __syncthreads();
-        if (s + 1 < nslabs) {
-#pragma unroll
-          for (int i = 0; i < EX_CPT; ++i) {
-            const int id = tid + EX_THREADS * i;
-            pre[i] = load_chunk<U>(a, s_row[id / EX_CPR], (s + 1) * KE + (id % EX_CPR) * PER);
-          }
-        }
-        if (nta == 0 || ntb == 0) continue;   // (wave-uniform; the barriers are above)
-#pragma unroll
-        for (int c = 0; c < EX_CPR / 4; ++c) {
-          if (s * KE + c * 4 * PER >= a.d) break;   // a group of chunks wholly past d: zeros
-          uint4 ra[EX_WM], rb[EX_WN];
-          const int at = (lane & 15) * EX_LDR + c * 64 + (lane >> 4) * 16;
-#pragma unroll
-          for (int t = 0; t < EX_WM; ++t)
-            ra[t] = *(const uint4*)(tile + (wm * 16 * EX_WM + t * 16) * EX_LDR + at);
-#pragma unroll
-          for (int u = 0; u < EX_WN; ++u)
-            rb[u] = *(const uint4*)(tile + (EX_BM + wn * 16 * EX_WN + u * 16) * EX_LDR + at);
-          MfmaSteps<DT, 0, PER>::run(ra, rb, nta, ntb, acc);
-        }
+        if (s + 1 < nslabs) ExTile::fetch<U>(a.src, s_row, (s + 1) * KE, ExTile::CPT, pre);
+        if (nta != 0 && ntb != 0)   // (wave-uniform; the barriers are above)
+          ExTile::mma<DT>(tile, wm * 16 * EX_WM, EX_BM + wn * 16 * EX_WN, lane, s, a.src.d, live,
+                          acc);
       }
-      // C/D of v_mfma_f64_16x16x4_f64: column = lane & 15, row = (lane >> 4) + 4 * register
       const double inv_w = s_inv_w;
+      // C/D of v_mfma_f64_16x16x4_f64 (pair_f64.h): column = lane & 15, row = (lane >> 4) + 4 * i
 #pragma unroll
       for (int t = 0; t < EX_WM; ++t) {
 #pragma unroll
         for (int u = 0; u < EX_WN; ++u) {
-          if (t >= nta || u >= ntb) continue;
+          if (!((live >> (t * EX_WN + u)) & 1u)) continue;
           const int ll = wn * 16 * EX_WN + u * 16 + (lane & 15);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int jj = wm * 16 * EX_WM + t * 16 + (lane >> 4) + 4 * i;
             if (jj < mrows && ll < nrows) {
-              const double v = s_row[jj] < 0 ? ex_nan()
+              const double v = s_row[jj] < 0 ? f64_nan()
                                              : contrib_term(s_w[ll], acc[t][u][i],
                                                             s_g[EX_BM + ll], s_g[jj], inv_w);
               outb[(int64_t)(m0 + jj) * Lb + n0 + ll] = v;
@@ -312,8 +183,7 @@ struct SelectArgs {
 // are one value. With largest == 0 the order is reversed (no key but NaN's is 0 or all ones).
 __device__ __forceinline__ uint64_t sel_key(double v, int largest) {
   if (!(v == v)) return 0ull;
-  const uint64_t u = v == 0.0 ? 0ull : (uint64_t)__double_as_longlong(v);
-  const uint64_t key = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  const uint64_t key = f64_key(v);
   return largest ? key : ~key;
 }
 
@@ -356,9 +226,7 @@ __global__ __launch_bounds__(256) void explain_select_kernel(const SelectArgs a)
           bp = (uint32_t)i;
         }
       }
-      const uint32_t hi = wave_max_u32((uint32_t)(bk >> 32));
-      const uint32_t lo = wave_max_u32((uint32_t)(bk >> 32) == hi ? (uint32_t)bk : 0u);
-      const uint64_t best = ((uint64_t)hi << 32) | lo;
+      const uint64_t best = wave_max_u64(bk);
       if (best == 0ull) break;   // nothing left (wave-uniform)
       const uint32_t p = wave_min_u32(bk == best ? bp : 0xFFFFFFFFu);
       if (lane == 0) {
@@ -370,26 +238,11 @@ __global__ __launch_bounds__(256) void explain_select_kernel(const SelectArgs a)
       pp = p;
     }
     for (int tt = t + lane; tt < a.m; tt += 64) {
-      a.val[seg * a.m + tt] = ex_nan();
+      a.val[seg * a.m + tt] = f64_nan();
       a.pos[seg * a.m + tt] = -1;
       a.row[seg * a.m + tt] = -1;
     }
   }
-}
-
-int64_t grid_of(int64_t items, int64_t cap) { return items < 1 ? 1 : (items > cap ? cap : items); }
-
-int check_catalog(const char* who, const ebt_catalog* cat) {
-  if (!cat || !cat->data || !cat->gnorm64) {
-    set_error("%s: null pointer", who);
-    return EBT_EINVAL;
-  }
-  if (cat->n < 1 || cat->d < 1 || cat->ld < cat->d || cat->dtype < 0 || cat->dtype > 3) {
-    set_error("%s: bad catalog (n=%lld d=%d ld=%lld dtype=%d)", who, (long long)cat->n, cat->d,
-              (long long)cat->ld, cat->dtype);
-    return EBT_EINVAL;
-  }
-  return EBT_OK;
 }
 
 }  // namespace
@@ -421,21 +274,15 @@ int ebt_liked_contrib(const ebt_catalog* cat, int64_t B, const int64_t* liked_of
     return EBT_EINVAL;
   }
   if (B == 0) return EBT_OK;
-  const int es = cat->dtype == EBT_F64 ? 8 : (cat->dtype == EBT_F32 ? 4 : 2);
   ExplainArgs a;
-  a.data = cat->data; a.ld = cat->ld; a.d = cat->d;
-  a.vec = ((uintptr_t)cat->data & 15) == 0 && (cat->ld * es) % 16 == 0;
-  a.gnorm = cat->gnorm64; a.row_offset = cat->row_offset; a.n = cat->n;
+  a.src = row_src(*cat);
   a.B = B; a.off = liked_off; a.lrows = liked_rows; a.lw = liked_w; a.rows = rows; a.k = k;
   a.out = out; a.status = status;
   const dim3 grid((unsigned)grid_of(B * ceil_div(k, EX_BM), 1 << 20)), block(EX_THREADS);
   hipStream_t st = (hipStream_t)stream;
-  switch (cat->dtype) {
-    case EBT_F32: hipLaunchKernelGGL(liked_contrib_kernel<EBT_F32>, grid, block, 0, st, a); break;
-    case EBT_BF16: hipLaunchKernelGGL(liked_contrib_kernel<EBT_BF16>, grid, block, 0, st, a); break;
-    case EBT_F16: hipLaunchKernelGGL(liked_contrib_kernel<EBT_F16>, grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL(liked_contrib_kernel<EBT_F64>, grid, block, 0, st, a); break;
-  }
+  for_dtype(cat->dtype, [&](auto dt) {
+    hipLaunchKernelGGL(liked_contrib_kernel<decltype(dt)::value>, grid, block, 0, st, a);
+  });
   return launch_check("liked_contrib_kernel");
 }
 

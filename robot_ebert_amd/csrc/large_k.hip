@@ -33,17 +33,6 @@ constexpr int LT = 64, LK = 16;
 constexpr int64_t LARGE_KEY_BUDGET = 1LL << 30;  // key bytes of one group of queries
 constexpr int64_t LARGE_GROUP_MAX = 64;
 
-__device__ __forceinline__ uint64_t score_key(double v) {
-  if (v != v) return 0ull;  // NaN: not a candidate (the key of an excluded row)
-  v += 0.0;  // -0 -> +0: one value, as they compare equal
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_score(uint64_t k) {
-  const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)u);
-}
-
 template <int DT>
 __global__ __launch_bounds__(256) void exact_keys_kernel(
     const double* __restrict__ q64, int64_t B, int d, const void* __restrict__ cat, int64_t ld,
@@ -98,7 +87,7 @@ __global__ __launch_bounds__(256) void exact_keys_kernel(
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t row = r0 + tx * 4 + j;
-      if (row < n) keys[qb * n + row] = score_key(acc[i][j] / gnorm[row]);
+      if (row < n) keys[qb * n + row] = f64_key(acc[i][j] / gnorm[row]);
     }
   }
 }
@@ -216,7 +205,7 @@ __global__ void large_out_kernel(const uint64_t* __restrict__ keys, const int32_
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < k;
        t += (int64_t)gridDim.x * blockDim.x) {
     const uint64_t key = t < n ? keys[q * n + t] : 0ull;
-    os[q * k + t] = key ? key_score(key) : __builtin_nan("");
+    os[q * k + t] = key ? key_f64(key) : __builtin_nan("");
     orow[q * k + t] = key ? (int64_t)rows[q * n + t] + row_offset : -1;
   }
 }

@@ -1881,16 +1881,6 @@ int finalize_topk(const float* cand_vals, const int64_t* cand_rows, const double
 // column ld-1); t_floor[b] = the k-th largest of g[r][b][j] - g[r][b][ld-1] over r, j (float64,
 // exact differences of two floats; NaN counts as -inf). One wave per query: bisection over the
 // order-preserving 64-bit keys of the doubles, counts by a strided pass over the R*(ld-1) values.
-__device__ __forceinline__ uint64_t d2key(double x) {
-  if (!(x == x)) return 0ull;  // NaN -> below -inf
-  uint64_t u = (uint64_t)__double_as_longlong(x);
-  if (x == 0.0) u = 0ull;      // -0 == +0
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key2d(uint64_t k) {
-  const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)u);
-}
 
 __global__ __launch_bounds__(256) void union_floor_kernel(const float* __restrict__ g, int R,
                                                           int64_t B, int ld, int k,
@@ -1908,7 +1898,7 @@ __global__ __launch_bounds__(256) void union_floor_kernel(const float* __restric
   };
   auto count_ge = [&](uint64_t t) {
     int c = 0;
-    for (int i = lane; i < n; i += 64) c += d2key(val(i)) >= t ? 1 : 0;
+    for (int i = lane; i < n; i += 64) c += f64_key(val(i)) >= t ? 1 : 0;
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
     return c;
   };
@@ -1919,7 +1909,7 @@ __global__ __launch_bounds__(256) void union_floor_kernel(const float* __restric
     if (count_ge(mid) >= k) lo = mid;
     else hi = mid - 1;
   }
-  if (lane == 0) t_floor[b] = lo == 0ull ? -__builtin_inf() : key2d(lo);
+  if (lane == 0) t_floor[b] = lo == 0ull ? -__builtin_inf() : key_f64(lo);
 }
 
 // The same bisection with the query's R*(ld-1) keys held in registers (up to 32 per lane), made
@@ -1967,7 +1957,7 @@ __global__ __launch_bounds__(256) void union_floor_reg_kernel(const float* __res
 #pragma unroll
   for (int e = 0; e < PL; ++e) {
     const bool in = t0 + STEP * e < n;
-    key[e] = in ? d2key((double)v[e] - (double)ev[e]) : 0ull;
+    key[e] = in ? f64_key((double)v[e] - (double)ev[e]) : 0ull;
     if (in) {
       mn = key[e] < mn ? key[e] : mn;
       mx = key[e] > mx ? key[e] : mx;
@@ -2014,7 +2004,7 @@ __global__ __launch_bounds__(256) void union_floor_reg_kernel(const float* __res
     if (c >= k) lo = mid;
     else hi = mid - 1;
   }
-  if (t0 == 0) t_floor[b] = lo == 0ull ? -__builtin_inf() : key2d(lo);
+  if (t0 == 0) t_floor[b] = lo == 0ull ? -__builtin_inf() : key_f64(lo);
 }
 
 // cert[b] = -1 (rerun unfused) when the fused screen overflowed (ovf[b] != 0) or the shared
