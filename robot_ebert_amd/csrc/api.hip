@@ -562,8 +562,8 @@ static int head_topk(const PipeArgs& a, const WsLayout& L, char* ws, int64_t r0,
     {
       StageScope s(timer, EBT_STAGE_GEMM, st);
       if (exact) {
-        const int es = c.dtype == EBT_F64 ? 8 : (c.dtype == EBT_F32 ? 4 : 2);
-        rc = screen_exact(q.q64, B, c.d, (const char*)c.cat + c0 * c.ld * es, c.dtype, c.ld,
+        rc = screen_exact(q.q64, B, c.d, (const char*)c.cat + c0 * c.ld * dtype_size(c.dtype),
+                          c.dtype, c.ld,
                           c.gnorm64 + c0, nc, S, L.ld_s, st);
       } else {
         rc = screen_gemm(q.qimg, q.B_pad, (const char*)c.cimg + c0 * c.ld_img * 2, nc, c.d_pad,

@@ -295,39 +295,29 @@ static int catalog_update(void* data, int dtype, int32_t d, int64_t ld, const in
     return EBT_EINVAL;
   }
   if (m == 0) return EBT_OK;
-  const int es = dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2);
-  const int ss = src_dtype == EBT_F64 ? 8 : (src_dtype == EBT_F32 ? 4 : 2);
   UpdArgs a;
   a.data = data; a.ld = ld; a.d = d; a.rows = rows; a.row_offset = row_offset; a.row0 = row0;
   a.m = m; a.src = src; a.ld_src = ld_src; a.gnorm = gnorm; a.inv32 = inv32;
   a.img = (uint16_t*)img; a.ld_img = ld_img; a.normalize = normalize; a.err_max = err_max;
-  a.src_vec = ((uintptr_t)src & 15) == 0 && (ld_src * ss) % 16 == 0;
-  a.cat_vec = ((uintptr_t)data & 15) == 0 && (ld * es) % 16 == 0;
+  a.src_vec = vec_ok(src, src_dtype, ld_src, 0);
+  a.cat_vec = vec_ok(data, dtype, ld, 0);
   a.stage = d <= UPD_STAGE_MAX_D;
-  // row_norms' own test for its vector form
-  const bool v = a.cat_vec && ((int64_t)d * es) % 16 == 0;
   int64_t blocks = ceil_div(m, 4);
   if (blocks > 4096) blocks = 4096;
   dim3 grid((unsigned)blocks), block(256);
   const size_t lds = a.stage ? (size_t)4 * d * sizeof(double) : 0;
-#define EBT_UP_V(DC, DS, IMG)                                                                  \
-  if (v) hipLaunchKernelGGL((catalog_update_kernel<DC, DS, IMG, true>), grid, block, lds, st, a); \
-  else hipLaunchKernelGGL((catalog_update_kernel<DC, DS, IMG, false>), grid, block, lds, st, a);
-#define EBT_UP(DC, IMG)                                  \
-  switch (src_dtype) {                                   \
-    case EBT_F32: EBT_UP_V(DC, EBT_F32, IMG) break;      \
-    case EBT_BF16: EBT_UP_V(DC, EBT_BF16, IMG) break;    \
-    case EBT_F16: EBT_UP_V(DC, EBT_F16, IMG) break;      \
-    default: EBT_UP_V(DC, EBT_F64, IMG) break;           \
-  }
-  switch (dtype) {
-    case EBT_F32: EBT_UP(EBT_F32, EBT_F16) break;
-    case EBT_BF16: EBT_UP(EBT_BF16, EBT_BF16) break;
-    case EBT_F16: EBT_UP(EBT_F16, EBT_F16) break;
-    default: EBT_UP(EBT_F64, EBT_F16) break;
-  }
-#undef EBT_UP
-#undef EBT_UP_V
+  // the image dtype follows the catalog's (want_img above), the source's is free; the last
+  // choice is row_norms' own test for its vector form
+  for_dtype(dtype, [&](auto dc) {
+    constexpr int DC = decltype(dc)::value, IMG = DC == EBT_BF16 ? EBT_BF16 : EBT_F16;
+    for_dtype(src_dtype, [&](auto ds) {
+      for_bool(vec_ok(data, dtype, ld, d), [&](auto vec) {
+        hipLaunchKernelGGL(
+            (catalog_update_kernel<DC, decltype(ds)::value, IMG, decltype(vec)::value>), grid,
+            block, lds, st, a);
+      });
+    });
+  });
   return launch_check("catalog_update_kernel");
 }
 
@@ -398,15 +388,14 @@ static int catalog_move(void* data, int dtype, int32_t d, int64_t ld, const int6
     return EBT_EINVAL;
   }
   if (p == 0) return EBT_OK;
-  const int es = dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2);
   MoveArgs a;
   a.data = data; a.ld = ld; a.d = d; a.moves = moves; a.p = p; a.n_new = n_new; a.n_old = n_old;
   a.gnorm = gnorm; a.inv32 = inv32; a.img = (uint16_t*)img; a.ld_img = ld_img;
-  a.cat_vec = ((uintptr_t)data & 15) == 0 && (ld * es) % 16 == 0;
+  a.cat_vec = vec_ok(data, dtype, ld, 0);
   int64_t blocks = ceil_div(p, 4);
   if (blocks > 4096) blocks = 4096;
   dim3 grid((unsigned)blocks), block(256);
-  switch (es) {
+  switch (dtype_size(dtype)) {
     case 8: hipLaunchKernelGGL((catalog_move_kernel<uint64_t>), grid, block, 0, st, a); break;
     case 4: hipLaunchKernelGGL((catalog_move_kernel<uint32_t>), grid, block, 0, st, a); break;
     default: hipLaunchKernelGGL((catalog_move_kernel<uint16_t>), grid, block, 0, st, a); break;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ebert.h"
@@ -278,12 +279,85 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t bk) {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 
+// ---- (score, row) lists: rescore.hip and shard_exchange.hip ---------------------------------
+constexpr int RTHREADS = 256;  // workgroup of the rescore, finalize and merge kernels
+
+__device__ __forceinline__ bool pair_before(double sa, int64_t ra, double sb, int64_t rb) {
+  return sa > sb || (sa == sb && ra < rb);
+}
+
+// Sort (score, row) pairs: score desc, row asc. P power of two.
+__device__ inline void bitonic_pairs(double* sc, int64_t* rw, int P) {
+  const int tid = threadIdx.x;
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < (P >> 1); t += blockDim.x) {
+        const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1));  // stride: a power of 2
+        const int hi = lo + stride;
+        const double a = sc[lo], b = sc[hi];
+        const int64_t ra = rw[lo], rb = rw[hi];
+        const bool first = (lo & size) == 0;  // this segment ends up in "before" order
+        const bool swap = first ? pair_before(b, rb, a, ra) : pair_before(a, ra, b, rb);
+        if (swap) {
+          sc[lo] = b;
+          sc[hi] = a;
+          rw[lo] = rb;
+          rw[hi] = ra;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// Marks v as used here, unconditionally: a load feeding only a guarded store would otherwise be
+// sunk into the guard's block and waited for there, one load at a time.
+__device__ __forceinline__ void issued(double v) { asm volatile("" : : "v"(v)); }
+__device__ __forceinline__ void issued(int64_t v) { asm volatile("" : : "v"(v)); }
+
 // Guarded norm: sklearn _handle_zeros_in_scale (preprocessing/_data.py:118-123).
 __device__ __forceinline__ double guard_norm(double nrm) {
   return nrm < 10.0 * 2.220446049250313e-16 ? 1.0 : nrm;
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int next_pow2_h(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+// ---- launch-site dispatch ------------------------------------------------------------------
+// A launch site names its kernel once, inside nested lambdas: f(std::integral_constant) for the
+// catalog dtype (four ways), the 16-bit image dtype (f16 / bf16) and a bool (vec / wave forms).
+// Only what a site nests is instantiated.
+template <typename F>
+inline void for_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case EBT_F32: f(std::integral_constant<int, EBT_F32>()); break;
+    case EBT_BF16: f(std::integral_constant<int, EBT_BF16>()); break;
+    case EBT_F16: f(std::integral_constant<int, EBT_F16>()); break;
+    default: f(std::integral_constant<int, EBT_F64>()); break;
+  }
+}
+template <typename F>
+inline void for_img(int img_dtype, F&& f) {
+  if (img_dtype == EBT_F16) f(std::integral_constant<int, EBT_F16>());
+  else f(std::integral_constant<int, EBT_BF16>());
+}
+template <typename F>
+inline void for_bool(bool v, F&& f) {
+  if (v) f(std::true_type());
+  else f(std::false_type());
+}
+// bytes per element of a catalog dtype
+inline int dtype_size(int dtype) { return dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2); }
+// rows of d elements, ld apart, that 16-byte vector loads can walk whole: an aligned base, row
+// stride and row length (d = 0: the row length is not asked about)
+inline bool vec_ok(const void* p, int dtype, int64_t ld, int d) {
+  const int es = dtype_size(dtype);
+  return (((uintptr_t)p & 15) == 0) && ((ld * es) % 16 == 0) && (((int64_t)d * es) % 16 == 0);
+}
 
 // Workspace regions are 256-byte aligned. carve: the region's offset; `o` moves past it
 inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }

@@ -201,10 +201,6 @@ int mask_allowed(float* s, int64_t ld, int64_t B, int64_t c0, int64_t c1, const 
 int rescore(const double* q64, int64_t B, const CatOps& c, const CandList& l, int32_t k,
             const float* eps, const double* t_floor, double* out_s, int64_t* out_r,
             int32_t* certified, const RescoreExtras& x, hipStream_t st);
-int merge_topk(const double* scores, const int64_t* rows, int32_t R, int64_t B, int32_t k,
-               double* out_s, int64_t* out_r, hipStream_t st);
-int shard_pack_lens(const double* scores, const int64_t* rows, int64_t B, int32_t k, int64_t cap,
-                    void* send, hipStream_t st);
 int screen_exact(const double* q64, int64_t B, int32_t d, const void* cat, int dtype, int64_t ld,
                  const double* gnorm, int64_t n_rows, float* S, int64_t ld_s, hipStream_t st);
 int export_list(int64_t* rows, int64_t B, int32_t kprime, int64_t row_offset, const int* ovf,
@@ -216,6 +212,12 @@ int rescore_owned(const double* q64, int64_t B, int32_t d, const void* cat, int 
 int finalize_topk(const float* cand_vals, const int64_t* cand_rows, const double* exact, int64_t B,
                   int32_t kprime, int32_t k, int64_t n_rows, const float* eps, const int32_t* ovf,
                   double* out_s, int64_t* out_r, int32_t* certified, hipStream_t st);
+
+// ---- shard_exchange.hip ----------------------------------------------------------------------
+int merge_topk(const double* scores, const int64_t* rows, int32_t R, int64_t B, int32_t k,
+               double* out_s, int64_t* out_r, hipStream_t st);
+int shard_pack_lens(const double* scores, const int64_t* rows, int64_t B, int32_t k, int64_t cap,
+                    void* send, hipStream_t st);
 int union_floor(const float* gathered, int32_t R, int64_t B, int32_t ld, int32_t k,
                 double* t_floor, hipStream_t stream, uint32_t* zero2);
 

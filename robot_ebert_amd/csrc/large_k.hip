@@ -5,7 +5,7 @@
 //
 // Per group of Bg queries (float64 scores of Bg x n as 64-bit order keys, ~1 GiB at most):
 //   exact_keys_kernel  key[b][i] = order key of (q64_b . c_i) / gnorm64_i (the float64 FMA
-//                      tiling of the EXACT screen, rescore.hip); a NaN score (a catalog row with
+//                      tile of the EXACT screen, exact_tile_f64.h); a NaN score (a catalog row with
 //                      a NaN / inf element) gets key 0 and is dropped like an excluded row: the
 //                      convention of every other path of the library, whose selects never take
 //                      a NaN (include/ebert.h, "Non-finite catalog rows")
@@ -23,13 +23,13 @@
 // Round 6: hand-written, replacing one radix sort per query through the CUB-compatible API.
 // A rare path (no caller of the reference asks for more than k = 100): plain, not tuned.
 #include "common.h"
+#include "exact_tile_f64.h"
 #include "internal.h"
 
 namespace ebt {
 
 namespace {
 
-constexpr int LT = 64, LK = 16;
 constexpr int64_t LARGE_KEY_BUDGET = 1LL << 30;  // key bytes of one group of queries
 constexpr int64_t LARGE_GROUP_MAX = 64;
 
@@ -37,56 +37,16 @@ template <int DT>
 __global__ __launch_bounds__(256) void exact_keys_kernel(
     const double* __restrict__ q64, int64_t B, int d, const void* __restrict__ cat, int64_t ld,
     const double* __restrict__ gnorm, int64_t n, uint64_t* __restrict__ keys) {
-  __shared__ double qs[LK][LT + 1], cs[LK][LT + 1];
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  const int64_t r0 = (int64_t)blockIdx.x * LT, b0 = (int64_t)blockIdx.y * LT;
   double acc[4][4] = {};
-  for (int k0 = 0; k0 < d; k0 += LK) {
-    // the tile's 4 elements per thread loaded before any is stored (guarded loads would each
-    // be waited for in turn): out-of-range indices read a clamped in-range element, then 0
-    constexpr int NE = LT * LK / 256;
-    double cv[NE], qv[NE];
-#pragma unroll
-    for (int u = 0; u < NE; ++u) {
-      const int e = tid + 256 * u;
-      const int rr = e / LK, kk = e % LK;
-      const int64_t row = r0 + rr, qb = b0 + rr;
-      const int kc = k0 + kk < d ? k0 + kk : d - 1;
-      cv[u] = load_as_f64<DT>(cat, (row < n ? row : n - 1) * ld + kc);
-      qv[u] = q64[(qb < B ? qb : B - 1) * d + kc];
-    }
-#pragma unroll
-    for (int u = 0; u < NE; ++u) {
-      const int e = tid + 256 * u;
-      const int rr = e / LK, kk = e % LK;
-      const int64_t row = r0 + rr, qb = b0 + rr;
-      const bool kin = k0 + kk < d;
-      cs[kk][rr] = (kin && row < n) ? cv[u] : 0.0;
-      qs[kk][rr] = (kin && qb < B) ? qv[u] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < LK; ++kk) {
-      double a[4], c[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        a[i] = qs[kk][ty * 4 + i];
-        c[i] = cs[kk][tx * 4 + i];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_fma(a[i], c[j], acc[i][j]);
-    }
-    __syncthreads();
-  }
+  int64_t q_at, r_at;
+  exact_tile_f64<DT>(q64, B, d, cat, ld, n, acc, q_at, r_at);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int64_t qb = b0 + ty * 4 + i;
+    const int64_t qb = q_at + i;
     if (qb >= B) continue;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int64_t row = r0 + tx * 4 + j;
+      const int64_t row = r_at + j;
       if (row < n) keys[qb * n + row] = f64_key(acc[i][j] / gnorm[row]);
     }
   }
@@ -247,26 +207,12 @@ int large_topk(const double* q64, int64_t B, int32_t d, const void* cat, int dty
   int rc = EBT_OK;
   for (int64_t b0 = 0; b0 < B; b0 += Bg) {
     const int64_t m = B - b0 < Bg ? B - b0 : Bg;
-    const dim3 grid((unsigned)ceil_div(n, LT), (unsigned)ceil_div(m, LT)), block(256);
+    const dim3 grid((unsigned)ceil_div(n, XT), (unsigned)ceil_div(m, XT)), block(256);
     const double* q = q64 + b0 * d;
-    switch (dtype) {
-      case EBT_F32:
-        hipLaunchKernelGGL(exact_keys_kernel<EBT_F32>, grid, block, 0, st, q, m, d, cat, ld, gnorm,
-                           n, k0);
-        break;
-      case EBT_BF16:
-        hipLaunchKernelGGL(exact_keys_kernel<EBT_BF16>, grid, block, 0, st, q, m, d, cat, ld,
-                           gnorm, n, k0);
-        break;
-      case EBT_F16:
-        hipLaunchKernelGGL(exact_keys_kernel<EBT_F16>, grid, block, 0, st, q, m, d, cat, ld, gnorm,
-                           n, k0);
-        break;
-      default:
-        hipLaunchKernelGGL(exact_keys_kernel<EBT_F64>, grid, block, 0, st, q, m, d, cat, ld, gnorm,
-                           n, k0);
-        break;
-    }
+    for_dtype(dtype, [&](auto dt) {
+      hipLaunchKernelGGL(exact_keys_kernel<decltype(dt)::value>, grid, block, 0, st, q, m, d, cat,
+                         ld, gnorm, n, k0);
+    });
     rc = launch_check("exact_keys_kernel");
     if (rc) return rc;
     if (excl_off) {

@@ -18,8 +18,6 @@
 // with the dot product afterwards is its own, one separately rounded operation at a time.
 #pragma once
 
-#include <type_traits>
-
 #include "common.h"
 
 namespace ebt {
@@ -37,10 +35,9 @@ struct RowSrc {
 };
 
 inline RowSrc row_src(const ebt_catalog& cat) {
-  const int es = cat.dtype == EBT_F64 ? 8 : (cat.dtype == EBT_F32 ? 4 : 2);
   RowSrc s;
   s.data = cat.data; s.ld = cat.ld; s.d = cat.d;
-  s.vec = ((uintptr_t)cat.data & 15) == 0 && (cat.ld * es) % 16 == 0;
+  s.vec = vec_ok(cat.data, cat.dtype, cat.ld, 0);
   s.gnorm = cat.gnorm64; s.row_offset = cat.row_offset; s.n = cat.n;
   return s;
 }
@@ -60,17 +57,6 @@ inline int check_catalog(const char* who, const ebt_catalog* cat) {
 
 inline int64_t grid_of(int64_t items, int64_t cap) {
   return items < 1 ? 1 : (items > cap ? cap : items);
-}
-
-// f(std::integral_constant<int, DT>) for the catalog's dtype (checked by check_catalog)
-template <typename F>
-inline void for_dtype(int dtype, F&& f) {
-  switch (dtype) {
-    case EBT_F32: f(std::integral_constant<int, EBT_F32>()); break;
-    case EBT_BF16: f(std::integral_constant<int, EBT_BF16>()); break;
-    case EBT_F16: f(std::integral_constant<int, EBT_F16>()); break;
-    default: f(std::integral_constant<int, EBT_F64>()); break;
-  }
 }
 
 __device__ __forceinline__ double f64_nan() { return __longlong_as_double(0x7ff8000000000000ll); }

@@ -66,11 +66,6 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const void* __restrict__
   }
 }
 
-static bool vec_ok(const void* p, int dtype, int64_t ld, int d) {
-  const int es = dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2);
-  return (((uintptr_t)p & 15) == 0) && ((ld * es) % 16 == 0) && (((int64_t)d * es) % 16 == 0);
-}
-
 int row_norms(const void* x, int dtype, int64_t n, int32_t d, int64_t ld, double* gnorm,
               float* inv32, hipStream_t st) {
   if (!x || !gnorm || n < 0 || d <= 0 || ld < d || dtype < 0 || dtype > 3) {
@@ -78,20 +73,13 @@ int row_norms(const void* x, int dtype, int64_t n, int32_t d, int64_t ld, double
     return EBT_EINVAL;
   }
   if (n == 0) return EBT_OK;
-  const bool v = vec_ok(x, dtype, ld, d);
   dim3 grid((unsigned)ceil_div(n, 4)), block(256);
-#define EBT_RN(DT)                                                                         \
-  if (v) hipLaunchKernelGGL((row_norms_kernel<DT, true>), grid, block, 0, st, x, n, d, ld, \
-                            gnorm, inv32);                                                 \
-  else hipLaunchKernelGGL((row_norms_kernel<DT, false>), grid, block, 0, st, x, n, d, ld,  \
-                          gnorm, inv32);
-  switch (dtype) {
-    case EBT_F32: EBT_RN(EBT_F32) break;
-    case EBT_BF16: EBT_RN(EBT_BF16) break;
-    case EBT_F16: EBT_RN(EBT_F16) break;
-    default: EBT_RN(EBT_F64) break;
-  }
-#undef EBT_RN
+  for_dtype(dtype, [&](auto dt) {
+    for_bool(vec_ok(x, dtype, ld, d), [&](auto vec) {
+      hipLaunchKernelGGL((row_norms_kernel<decltype(dt)::value, decltype(vec)::value>), grid,
+                         block, 0, st, x, n, d, ld, gnorm, inv32);
+    });
+  });
   return launch_check("row_norms_kernel");
 }
 
@@ -221,29 +209,15 @@ int screen_image(const void* x, int dtype, int64_t n, int32_t d, int64_t ld,
   int64_t blocks = ceil_div(n, 4);  // one wave per row, 4 waves per block
   if (blocks > (1 << 20)) blocks = 1 << 20;
   dim3 grid((unsigned)blocks), block(256);
-  const int es = dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2);
-  const bool vec = ((uintptr_t)x & 15) == 0 && (ld * es) % 16 == 0;
-#define EBT_SI_V(DT, IMG)                                                                      \
-  if (vec)                                                                                     \
-    hipLaunchKernelGGL((screen_image_kernel<DT, IMG, true>), grid, block, 0, st, x, n, d, ld,  \
-                       gnorm, normalize, (uint16_t*)img, ld_img, err_max);                     \
-  else                                                                                         \
-    hipLaunchKernelGGL((screen_image_kernel<DT, IMG, false>), grid, block, 0, st, x, n, d, ld, \
-                       gnorm, normalize, (uint16_t*)img, ld_img, err_max);
-#define EBT_SI(DT)                                                                             \
-  if (img_dtype == EBT_F16) {                                                                  \
-    EBT_SI_V(DT, EBT_F16)                                                                      \
-  } else {                                                                                     \
-    EBT_SI_V(DT, EBT_BF16)                                                                     \
-  }
-  switch (dtype) {
-    case EBT_F32: EBT_SI(EBT_F32) break;
-    case EBT_BF16: EBT_SI(EBT_BF16) break;
-    case EBT_F16: EBT_SI(EBT_F16) break;
-    default: EBT_SI(EBT_F64) break;
-  }
-#undef EBT_SI
-#undef EBT_SI_V
+  for_dtype(dtype, [&](auto dt) {
+    for_img(img_dtype, [&](auto im) {
+      for_bool(vec_ok(x, dtype, ld, 0), [&](auto vec) {
+        hipLaunchKernelGGL(
+            (screen_image_kernel<decltype(dt)::value, decltype(im)::value, decltype(vec)::value>),
+            grid, block, 0, st, x, n, d, ld, gnorm, normalize, (uint16_t*)img, ld_img, err_max);
+      });
+    });
+  });
   return launch_check("screen_image_kernel");
 }
 
@@ -283,12 +257,10 @@ int query_dense(const void* q, int dtype, int64_t B, int32_t d, int64_t ldq, dou
   }
   if (B == 0) return EBT_OK;
   dim3 grid((unsigned)B), block(256);
-  switch (dtype) {
-    case EBT_F32: hipLaunchKernelGGL(query_dense_kernel<EBT_F32>, grid, block, 0, st, q, d, ldq, q64); break;
-    case EBT_BF16: hipLaunchKernelGGL(query_dense_kernel<EBT_BF16>, grid, block, 0, st, q, d, ldq, q64); break;
-    case EBT_F16: hipLaunchKernelGGL(query_dense_kernel<EBT_F16>, grid, block, 0, st, q, d, ldq, q64); break;
-    default: hipLaunchKernelGGL(query_dense_kernel<EBT_F64>, grid, block, 0, st, q, d, ldq, q64); break;
-  }
+  for_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(query_dense_kernel<decltype(dt)::value>, grid, block, 0, st, q, d, ldq,
+                       q64);
+  });
   return launch_check("query_dense_kernel");
 }
 
@@ -400,28 +372,18 @@ int query_liked_sum(const void* cat, int dtype, int32_t d, int64_t ld, const dou
   }
   if (B == 0) return EBT_OK;
   dim3 grid((unsigned)B), block(256);
-  const int es = dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2);
-  const int per = 16 / es;
-  if (((uintptr_t)cat & 15) == 0 && (ld * es) % 16 == 0 && d % per == 0 && d <= 256 * per * 2) {
-#define EBT_QLV(DT)                                                                            \
-  hipLaunchKernelGGL(query_liked_vec_kernel<DT>, grid, block, 0, st, cat, d, ld, gnorm, off,   \
-                     rows, row_offset, n_local, q64)
-    switch (dtype) {
-      case EBT_F32: EBT_QLV(EBT_F32); break;
-      case EBT_BF16: EBT_QLV(EBT_BF16); break;
-      case EBT_F16: EBT_QLV(EBT_F16); break;
-      default: EBT_QLV(EBT_F64); break;
-    }
-#undef EBT_QLV
-    return launch_check("query_liked_vec_kernel");
-  }
-  switch (dtype) {
-    case EBT_F32: hipLaunchKernelGGL(query_liked_kernel<EBT_F32>, grid, block, 0, st, cat, d, ld, gnorm, off, rows, row_offset, n_local, q64); break;
-    case EBT_BF16: hipLaunchKernelGGL(query_liked_kernel<EBT_BF16>, grid, block, 0, st, cat, d, ld, gnorm, off, rows, row_offset, n_local, q64); break;
-    case EBT_F16: hipLaunchKernelGGL(query_liked_kernel<EBT_F16>, grid, block, 0, st, cat, d, ld, gnorm, off, rows, row_offset, n_local, q64); break;
-    default: hipLaunchKernelGGL(query_liked_kernel<EBT_F64>, grid, block, 0, st, cat, d, ld, gnorm, off, rows, row_offset, n_local, q64); break;
-  }
-  return launch_check("query_liked_kernel");
+  // the chunk form: whole 16-byte chunks, at most two per thread
+  const bool vec = vec_ok(cat, dtype, ld, d) && d <= 256 * (16 / dtype_size(dtype)) * 2;
+  for_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, block, 0, st, cat, d, ld, gnorm, off, rows, row_offset,
+                         n_local, q64);
+    };
+    if (vec) launch(query_liked_vec_kernel<DT>);
+    else launch(query_liked_kernel<DT>);
+  });
+  return launch_check(vec ? "query_liked_vec_kernel" : "query_liked_kernel");
 }
 
 // ------------------------------------------------------- weighted liked rows (ABI 0.8.0) ----
@@ -535,24 +497,16 @@ int query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld, const do
   }
   if (B == 0) return EBT_OK;
   dim3 grid((unsigned)B), block(256);
-  const int es = dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2);
-  const int per = 16 / es;
-  const bool vec = ((uintptr_t)cat & 15) == 0 && (ld * es) % 16 == 0 && d % per == 0 &&
-                   d <= 256 * per * 2;
-#define EBT_QLW(DT)                                                                            \
-  if (vec)                                                                                     \
-    hipLaunchKernelGGL(query_liked_w_vec_kernel<DT>, grid, block, 0, st, cat, d, ld, gnorm,    \
-                       off, rows, wts, row_offset, n_local, q64);                              \
-  else                                                                                         \
-    hipLaunchKernelGGL(query_liked_w_kernel<DT>, grid, block, 0, st, cat, d, ld, gnorm, off,   \
-                       rows, wts, row_offset, n_local, q64)
-  switch (dtype) {
-    case EBT_F32: EBT_QLW(EBT_F32); break;
-    case EBT_BF16: EBT_QLW(EBT_BF16); break;
-    case EBT_F16: EBT_QLW(EBT_F16); break;
-    default: EBT_QLW(EBT_F64); break;
-  }
-#undef EBT_QLW
+  const bool vec = vec_ok(cat, dtype, ld, d) && d <= 256 * (16 / dtype_size(dtype)) * 2;
+  for_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, block, 0, st, cat, d, ld, gnorm, off, rows, wts, row_offset,
+                         n_local, q64);
+    };
+    if (vec) launch(query_liked_w_vec_kernel<DT>);
+    else launch(query_liked_w_kernel<DT>);
+  });
   return launch_check(vec ? "query_liked_w_vec_kernel" : "query_liked_w_kernel");
 }
 
@@ -845,26 +799,20 @@ int query_prep(const void* q, int dtype, int64_t B, int64_t B_pad, int32_t d, in
     return EBT_EINVAL;
   }
   if (B_pad == 0) return EBT_OK;
-  const int es = dtype == EBT_F64 ? 8 : (dtype == EBT_F32 ? 4 : 2);
-  const bool wave = d % 8 == 0 && d <= 64 * 8 * QPW_CH && ((uintptr_t)q & 15) == 0 &&
-                    (ldq * es) % 16 == 0 && ((uintptr_t)q64 & 15) == 0 &&
-                    ((uintptr_t)qimg & 15) == 0;
+  const bool wave = d % 8 == 0 && d <= 64 * 8 * QPW_CH && vec_ok(q, dtype, ldq, 0) &&
+                    ((uintptr_t)q64 & 15) == 0 && ((uintptr_t)qimg & 15) == 0;
   dim3 grid(wave ? (unsigned)ceil_div(B_pad, 4) : (unsigned)B_pad), block(256);
-#define EBT_QP(DT, IMG)                                                                        \
-  if (wave)                                                                                    \
-    hipLaunchKernelGGL((query_prep_wave_kernel<DT, IMG>), grid, block, 0, st, q, B, B_pad, d,  \
-                       ldq, native_q, u_cat, q64, (uint16_t*)qimg, ld_img, qscale, eps);       \
-  else                                                                                         \
-    hipLaunchKernelGGL((query_prep_kernel<DT, IMG>), grid, block, 0, st, q, B, d, ldq,         \
-                       native_q, u_cat, q64, (uint16_t*)qimg, ld_img, qscale, eps)
-  const bool f16 = img_dtype == EBT_F16;
-  switch (dtype) {
-    case EBT_F32: if (f16) { EBT_QP(EBT_F32, EBT_F16); } else { EBT_QP(EBT_F32, EBT_BF16); } break;
-    case EBT_BF16: if (f16) { EBT_QP(EBT_BF16, EBT_F16); } else { EBT_QP(EBT_BF16, EBT_BF16); } break;
-    case EBT_F16: if (f16) { EBT_QP(EBT_F16, EBT_F16); } else { EBT_QP(EBT_F16, EBT_BF16); } break;
-    default: if (f16) { EBT_QP(EBT_F64, EBT_F16); } else { EBT_QP(EBT_F64, EBT_BF16); } break;
-  }
-#undef EBT_QP
+  for_dtype(dtype, [&](auto dt) {
+    for_img(img_dtype, [&](auto im) {
+      constexpr int DT = decltype(dt)::value, IMG = decltype(im)::value;
+      if (wave)
+        hipLaunchKernelGGL((query_prep_wave_kernel<DT, IMG>), grid, block, 0, st, q, B, B_pad, d,
+                           ldq, native_q, u_cat, q64, (uint16_t*)qimg, ld_img, qscale, eps);
+      else
+        hipLaunchKernelGGL((query_prep_kernel<DT, IMG>), grid, block, 0, st, q, B, d, ldq,
+                           native_q, u_cat, q64, (uint16_t*)qimg, ld_img, qscale, eps);
+    });
+  });
   return launch_check(wave ? "query_prep_wave_kernel" : "query_prep_kernel");
 }
 

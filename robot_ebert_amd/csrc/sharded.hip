@@ -124,7 +124,7 @@ bool shard_layout(const ebt_catalog& c, const ebt_comm& cm, int64_t B, int32_t k
   L.off_lr = carve(o, (size_t)B * kp * 8);
   L.off_ovf = carve(o, (size_t)B * 4);
   L.off_eps = carve(o, (size_t)B * 4);
-  // the compact exchange (rescore.hip): each shard's w best approx for the floor, its entries
+  // the compact exchange (shard_exchange.hip): each shard's w best approx for the floor, its entries
   // above the floor for the results (int32 rows behind per-query starts)
   L.fw = ebt_shard_list_width(k, (int32_t)R);
   L.cap = ebt_shard_pack_cap(B, k, (int32_t)R, cm.n_global);

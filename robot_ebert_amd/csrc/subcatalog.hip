@@ -355,7 +355,6 @@ int ebt_catalog_gather_rows(const ebt_catalog* parent, const int64_t* rows, int6
               "16-byte aligned", who, c.ld_img);
     return EBT_EINVAL;
   }
-  const int es = c.dtype == EBT_F64 ? 8 : (c.dtype == EBT_F32 ? 4 : 2);
   GatherArgs a;
   a.data = c.data; a.ld = c.ld; a.d = c.d; a.rows = rows; a.row_offset = c.row_offset; a.n = c.n;
   a.m = m; a.data_out = data_out; a.ld_out = ld_out; a.gnorm = c.gnorm64; a.inv32 = c.inv32;
@@ -363,11 +362,10 @@ int ebt_catalog_gather_rows(const ebt_catalog* parent, const int64_t* rows, int6
   a.img = alias ? nullptr : (const uint16_t*)c.image;
   a.img_out = alias ? nullptr : (uint16_t*)image_out;
   a.ld_img = c.ld_img;
-  a.vec = ((uintptr_t)c.data & 15) == 0 && (c.ld * es) % 16 == 0 &&
-          ((uintptr_t)data_out & 15) == 0 && (ld_out * es) % 16 == 0;
+  a.vec = vec_ok(c.data, c.dtype, c.ld, 0) && vec_ok(data_out, c.dtype, ld_out, 0);
   const dim3 grid((unsigned)grid_for(m, 4, 1 << 16)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  switch (es) {
+  switch (dtype_size(c.dtype)) {
     case 8: hipLaunchKernelGGL((catalog_gather_kernel<uint64_t>), grid, block, 0, st, a); break;
     case 4: hipLaunchKernelGGL((catalog_gather_kernel<uint32_t>), grid, block, 0, st, a); break;
     default: hipLaunchKernelGGL((catalog_gather_kernel<uint16_t>), grid, block, 0, st, a); break;
