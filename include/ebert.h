@@ -92,7 +92,11 @@ extern "C" {
  *        struct, signature or workspace size changes).
  * 0.10.0: diversified top-k, greedy maximal marginal relevance over a candidate pool:
  *        ebt_mmr_workspace_bytes, ebt_pool_gram, ebt_mmr_select, ebt_mmr_topk (additive; no
- *        existing entry, struct, kernel or workspace size changes). */
+ *        existing entry, struct, kernel or workspace size changes).
+ * 0.11.0: multi-interest top-k, cluster the liked rows and interleave the per-cluster answers:
+ *        ebt_interest_workspace_bytes, ebt_interest_cluster, ebt_liked_interests,
+ *        ebt_interest_interleave (additive; no existing entry, struct, kernel or workspace size
+ *        changes). */
 int ebt_version(void);
 
 /* Message for the last non-zero return on this thread ("" if none). */
@@ -1028,6 +1032,88 @@ int ebt_mmr_topk(const ebt_catalog* cat, int64_t B, const double* rel, const int
                  int32_t p, int32_t k, double lam, void* workspace, size_t ws_bytes,
                  int32_t* out_pos, int64_t* out_rows, double* out_rel, double* out_mmr,
                  int32_t* status, void* stream);
+
+/* ---- multi-interest top-k (0.11.0): cluster the liked rows, interleave the answers ------------
+ * The reference scores a user as the mean cosine to everything they liked (lib.py:51-52), so a
+ * user with several distinct tastes is searched at the centroid of those tastes. These entries
+ * group the liked rows of a query into up to c clusters and merge the top-k lists searched once
+ * per cluster, each cluster taking output slots in proportion to its size.
+ *
+ * rows [B][p]: GLOBAL rows of ONE unsharded catalog, -1 = an empty slot anywhere in the list,
+ * 1 <= p <= EBT_MMR_POOL_MAX. The "position" of a row is its slot in that list.
+ *
+ * ebt_interest_cluster, per query, with S = that query's gram [p][p] (what ebt_pool_gram wrote:
+ * bitwise symmetric). Everything is float64 and every operation is rounded on its own; -0 equals
+ * +0 in comparisons:
+ *
+ *   valid_i = rows[i] >= 0;  L = #valid;  c_eff = min(c, L)
+ *   L == 0: label = -1, size = 0, medoid = -1, iters = 0
+ *   tot_i = +0.0; for j ascending over valid j: tot_i = tot_i + S(i, j)            (valid i)
+ *   seed_0 = arg max by (tot desc, position asc);  near_i = S(seed_0, i)
+ *   for m = 1 .. c_eff-1:
+ *       seed_m = arg min over valid non-seed i by (near asc, position asc)
+ *       near_i = S(seed_m, i) > near_i ? S(seed_m, i) : near_i
+ *   label_i = arg max over m < c_eff by (S(seed_m, i) desc, m asc);  label_{seed_m} = m
+ *   PASS(label): n_m = #{i: label_i = m}
+ *                acc_{i,m} = +0.0; for j ascending over valid j: acc_{i,label_j} = acc_{i,label_j} + S(i, j)
+ *                mean_{i,m} = acc_{i,m} / (double) n_m           (only for n_m > 0)
+ *   for it = 1 .. EBT_INTEREST_ITERS:
+ *       PASS(label); new_i = arg max over m with n_m > 0 by (mean_{i,m} desc, m asc)
+ *       iters = it;  if new == label everywhere: break;  label = new
+ *   PASS(label) once more if the loop ended at the cap (otherwise the last pass's values are the
+ *   final ones)
+ *   medoid_m = arg max over the members i of m by (mean_{i,m} desc, position asc); -1 if n_m == 0
+ *   renumber the clusters by (n desc, lowest member position asc), empty ones last; outputs use
+ *   the new numbers; out_size[m] = n_m (0 for m >= the number of non-empty clusters);
+ *   out_label = -1 on empty slots
+ *
+ * mean_{i,m} is the reference's own score of row i against the list "cluster m" (lib.py:51-52):
+ * a liked row joins the cluster that would recommend it most strongly. out_medoid holds
+ * positions. The result does not depend on where the -1 slots are, on how far the list is padded
+ * or on the other queries of the batch. (A NaN in S between valid slots is outside the contract:
+ * it ranks last in every arg max / arg min and the outputs stay within range.) status may be
+ * NULL; a query with status[b] < 0 gets all-empty outputs.
+ *
+ * ebt_liked_interests: ebt_pool_gram into a caller's workspace of
+ * ebt_interest_workspace_bytes(B, p) = ebt_mmr_workspace_bytes(B, p) bytes, then
+ * ebt_interest_cluster (ebt_mmr_topk's composition). A row outside the catalog is never read:
+ * status[b] = -2 and that query's outputs are all empty.
+ *
+ * ebt_interest_interleave, per query: cluster m gets output slots in proportion to size[m] by
+ * the highest-averages (D'Hondt) rule in integer arithmetic; list_rows / list_scores [B][c][k]
+ * are the per-cluster results (-1 / anything = an empty slot):
+ *
+ *   taken_m = 0; next_m = 0
+ *   for t = 0 .. k-1:
+ *       every m: while next_m < k and (list_rows[m][next_m] < 0 or that row was already
+ *                emitted): next_m++
+ *       live = {m: size_m > 0 and next_m < k};  none: stop
+ *       m* = the live m with the largest size_m / (taken_m + 1), compared exactly: a beats b iff
+ *            size_a * (taken_b + 1) > size_b * (taken_a + 1), or these are equal and a < b (int64)
+ *       out_rows[t] = list_rows[m*][next_m*]; out_scores[t] = its score, the input's bits;
+ *       out_cluster[t] = m*; out_pos[t] = next_m*;  taken_m*++; next_m*++
+ *   slots past the stop: -1 / NaN / -1 / -1
+ *
+ * Found on the host before any GPU call, EBT_EINVAL with a message that starts with the entry's
+ * name: a null pointer, p outside [1, EBT_MMR_POOL_MAX], c outside [1, EBT_INTEREST_MAX], k
+ * outside [1, EBT_INTEREST_K_MAX], B < 0 (for the clustering also B > 4 * (2^31 - 1): one wave
+ * per query, four per workgroup), a catalog whose ld < d, a workspace that is too small.
+ * B == 0 returns EBT_OK without a launch. No timer stage is recorded. */
+#define EBT_INTEREST_MAX 8      /* clusters per query */
+#define EBT_INTEREST_ITERS 16   /* reassignment passes */
+#define EBT_INTEREST_K_MAX 512
+size_t ebt_interest_workspace_bytes(int64_t B, int32_t p);
+int ebt_interest_cluster(const double* gram, const int64_t* rows, int64_t B, int32_t p, int32_t c,
+                         const int32_t* status, int32_t* out_label, int32_t* out_size,
+                         int32_t* out_medoid, int32_t* out_iters, void* stream);
+int ebt_liked_interests(const ebt_catalog* cat, int64_t B, const int64_t* rows, int32_t p,
+                        int32_t c, void* workspace, size_t ws_bytes, int32_t* out_label,
+                        int32_t* out_size, int32_t* out_medoid, int32_t* out_iters,
+                        int32_t* status, void* stream);
+int ebt_interest_interleave(const int32_t* size, const int64_t* list_rows,
+                            const double* list_scores, int64_t B, int32_t c, int32_t k,
+                            int64_t* out_rows, double* out_scores, int32_t* out_cluster,
+                            int32_t* out_pos, void* stream);
 
 /* ---- two-phase top-k over a row-sharded catalog (robot_ebert_amd/distributed.py) ---------
  * Phase 1, every rank: ebt_cosine_screen = ebt_cosine_topk_prepared without the rescore: the shard's k'

@@ -26,6 +26,11 @@ each score and the m largest of them; ``lib.get_user_recs_explained`` attaches t
 ``diversify_topk`` (ABI 0.10.0) trades relevance for variety: from a pool of the p best rows it
 picks k greedily by maximal marginal relevance, lam * score - (1 - lam) * (largest cosine to a
 row already picked); ``lib.get_user_recs_diverse`` is the recommend call over it.
+
+``multi_interest_topk`` (ABI 0.11.0) serves a user with several tastes: ``cluster_liked`` groups
+the liked rows into up to c clusters, each cluster is searched on its own, and the answers are
+interleaved in proportion to the clusters' sizes; ``lib.get_user_recs_interests`` is the recommend
+call over it ("more like X", X the cluster's medoid).
 """
 from ._lib import EbertError, Timer, load  # noqa: F401
 from .catalog import Catalog  # noqa: F401
@@ -34,6 +39,8 @@ from .search import (merge_topk, prepare_queries, rescore_rows, score_topk,  # n
                      score_topk_finish, score_topk_submit)
 from .explain import Explanation, explain_topk  # noqa: F401
 from .diversify import Diversified, diversify_topk  # noqa: F401
+from .interests import (Interests, MultiInterest, cluster_liked,  # noqa: F401
+                        multi_interest_topk)
 from . import ops  # noqa: F401,E402  (registers torch.ops.ebert.*)
 
 __version__ = "0.1.0"

@@ -28,6 +28,9 @@ EBT_FLAG_LIKED_CHECKED = 8   # ebert.h: the liked CSR was checked on the host (n
 EBT_FILTER_SLOTS_MAX = 128
 EBT_EXPLAIN_M_MAX = 64       # ebert.h: the most reasons ebt_explain_select returns per row
 EBT_MMR_POOL_MAX = 512       # ebert.h: the largest candidate pool of ebt_pool_gram / ebt_mmr_*
+EBT_INTEREST_MAX = 8         # ebert.h: the most clusters of ebt_interest_cluster / _interleave
+EBT_INTEREST_ITERS = 16      # ebert.h: the reassignment passes of ebt_interest_cluster
+EBT_INTEREST_K_MAX = 512     # ebert.h: the largest k of ebt_interest_interleave
 
 
 class EbertError(RuntimeError):
@@ -155,6 +158,12 @@ _SIGNATURES = {
                         _VP, _VP], _INT),
     "ebt_mmr_topk": ([_PCAT, _I64, _VP, _VP, _I32, _I32, ctypes.c_double, _VP, _SZ, _VP, _VP,
                       _VP, _VP, _VP, _VP], _INT),
+    "ebt_interest_workspace_bytes": ([_I64, _I32], _SZ),
+    "ebt_interest_cluster": ([_VP, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP], _INT),
+    "ebt_liked_interests": ([_PCAT, _I64, _VP, _I32, _I32, _VP, _SZ, _VP, _VP, _VP, _VP, _VP,
+                             _VP], _INT),
+    "ebt_interest_interleave": ([_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP],
+                                _INT),
     "ebt_sharded_workspace_bytes": ([_PCAT, _PCOMM, _I64, _I32, _POPT], _SZ),
     "ebt_cosine_topk_sharded": ([_PCAT, _PCOMM, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP,
                                  _POPT, _VP, _SZ, _VP, _VP, _VP, _VP], _INT),

@@ -16,7 +16,7 @@ from typing import List, Optional
 from fastapi import APIRouter, FastAPI, Query
 
 from . import lib
-from .models import ExplainedRecommendation, Recommendation
+from .models import ExplainedRecommendation, InterestRecommendation, Recommendation
 
 router = APIRouter()
 # a batcher.RecBatcher installed by app(batcher=...): the handler's scoring step is then
@@ -50,6 +50,16 @@ def get_user_recommendations_diverse(user_id: str, k: int = 10,
     order: lam = 1 is the plain top k, smaller values trade relevance for variety (no
     counterpart in the reference; never batched)"""
     return lib.get_user_recs_diverse(user_id=user_id, k=k, lam=lam, pool=pool)
+
+
+@router.get("/users/{user_id}/recommendations/interests/")
+def get_user_recommendations_interests(user_id: str, k: int = 10,
+                                       interests: int = Query(3, ge=1, le=8)
+                                       ) -> List[InterestRecommendation]:
+    """k recommendations drawn from up to `interests` clusters of the user's liked movies in
+    proportion to the clusters' sizes, each with the cluster's most central liked movie as its
+    anchor (no counterpart in the reference; never batched)"""
+    return lib.get_user_recs_interests(user_id=user_id, k=k, interests=interests)
 
 
 def app(batcher=None) -> FastAPI:

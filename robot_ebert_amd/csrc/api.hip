@@ -626,7 +626,7 @@ using namespace ebt;
 
 extern "C" {
 
-int ebt_version(void) { return 1000; }  // 0.10.0: diversified top-k, greedy MMR over a pool (ebert.h)
+int ebt_version(void) { return 1100; }  // 0.11.0: multi-interest top-k, cluster + interleave (ebert.h)
 
 const char* ebt_last_error(void) { return g_err; }
 

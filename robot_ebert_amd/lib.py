@@ -21,7 +21,8 @@ from sqlalchemy import select
 
 from . import tables
 from .catalog import Catalog
-from .models import ExplainedRecommendation, Movie, Reason, Recommendation
+from .models import (ExplainedRecommendation, InterestRecommendation, Movie, Reason,
+                     Recommendation)
 from .search import csr_from_lists, prepare_queries, rescore_rows, score_topk
 
 LIKED_MOVIE_SCORE = 3.5   # constants.py:19
@@ -328,6 +329,38 @@ def get_user_recs_diverse(user_id: str, k: int = 10, lam: float = 0.7,
              if rr >= 0]
     movies = {m.tmdb_id: m for m in get_movies(tmdb_ids=sorted(t for t, _ in pairs))}
     return [Recommendation(movie=movies[t], score=sc) for t, sc in pairs if t in movies]
+
+
+def get_user_recs_interests(user_id: str, k: int = 10,
+                            interests: int = 3) -> List[InterestRecommendation]:
+    """``get_user_recs`` for a user with several tastes: the same SQL, liked / rated sets and
+    errors (``[]`` for a user without ratings, sklearn's ValueError for one without a liked
+    movie), but the liked movies are grouped into up to ``interests`` clusters, each cluster is
+    searched as a liked list of its own, and the k movies are drawn from the clusters' answers in
+    proportion to their sizes (``interests.multi_interest_topk``; interests = 1 is the plain top
+    k).
+
+    Returns ``InterestRecommendation(movie, score, interest, anchor_tmdb_id)`` in INTERLEAVE
+    order: the score is the mean cosine to the liked movies of the movie's interest, the anchor
+    that interest's medoid ("more like X"). Movies are paired with their values by tmdb_id; one
+    that ``movies`` lacks is dropped (there is no reference order to mimic here, so lib.py:58-62's
+    zip -- SURVEY a-8 -- is not reproduced). A row-sharded catalog raises EbertError."""
+    from . import interests as _interests
+    _interests._check_c(interests)
+    req = _user_request(user_id)
+    if req is None:
+        return []
+    liked, rated = req
+    cat = movies_collab_catalog
+    got = _interests.multi_interest_topk(cat, k, liked=[liked], c=interests, exclude=[rated])
+    anchor = [cat.id_of(int(r)) if r >= 0 else "" for r in got.medoid_row[0].cpu().numpy()]
+    items = [(cat.id_of(int(rr)), float(ss), int(cc))
+             for rr, ss, cc in zip(got.rows[0].cpu().numpy(), got.scores[0].cpu().numpy(),
+                                   got.cluster[0].cpu().numpy()) if rr >= 0]
+    movies = {m.tmdb_id: m for m in get_movies(tmdb_ids=sorted(t for t, _, _ in items))}
+    return [InterestRecommendation(movie=movies[t], score=sc, interest=cl,
+                                   anchor_tmdb_id=anchor[cl])
+            for t, sc, cl in items if t in movies]
 
 
 def get_user_recs_batched(batcher, user_id: str, k: int = 10, allow=None,

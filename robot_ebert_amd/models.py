@@ -45,3 +45,10 @@ class ExplainedRecommendation(BaseModel):
     movie: Movie
     score: float
     reasons: List[Reason]
+
+
+class InterestRecommendation(BaseModel):  # (no counterpart in the reference)
+    movie: Movie
+    score: float          # the mean cosine to the liked movies of ITS interest (lib.py:51-52)
+    interest: int         # which of the user's interests it came from, 0 = the largest
+    anchor_tmdb_id: str   # that interest's most central liked movie: "more like X"
