@@ -96,7 +96,11 @@ extern "C" {
  * 0.11.0: multi-interest top-k, cluster the liked rows and interleave the per-cluster answers:
  *        ebt_interest_workspace_bytes, ebt_interest_cluster, ebt_liked_interests,
  *        ebt_interest_interleave (additive; no existing entry, struct, kernel or workspace size
- *        changes). */
+ *        changes).
+ * 0.12.0: grouped top-k, one list per (query, group) from one scoring pass:
+ *        ebt_grouped_pass_groups, ebt_select_topk_grouped, ebt_cosine_topk_grouped_workspace,
+ *        ebt_cosine_topk_grouped_prepared (additive; no existing entry, struct, kernel or
+ *        workspace size changes). */
 int ebt_version(void);
 
 /* Message for the last non-zero return on this thread ("" if none). */
@@ -1114,6 +1118,70 @@ int ebt_interest_interleave(const int32_t* size, const int64_t* list_rows,
                             const double* list_scores, int64_t B, int32_t c, int32_t k,
                             int64_t* out_rows, double* out_scores, int32_t* out_cluster,
                             int32_t* out_pos, void* stream);
+
+/* ---- grouped top-k (0.12.0): the k best rows of every category from one scoring pass ---------
+ * The reference keeps one list per user (lib.py:51-55); a front page shows a shelf per genre.
+ * With allow masks alone that is G calls of the masked pipeline, each repeating the B x N
+ * screening GEMM for the same query vectors. These entries score once and keep one list per
+ * (query, group).
+ *
+ * The contract: for B queries and G mask ids groups[0..G) into ONE allow table (masks, words,
+ * n_masks: the fields of ebt_allow above, bits indexed by GLOBAL row), the block
+ * out[g][0..B)[0..k) of ebt_cosine_topk_grouped_prepared is bit for bit what
+ * ebt_cosine_topk_prepared_allowed writes for the same operands with mask_id[b] = groups[g] for
+ * every b, run unfused at the same chunk_rows and kprime: the same GLOBAL rows, float64 scores,
+ * order (score descending, row ascending), NaN / -1 past the group's candidates, and the same
+ * certificate in certified[g][b] (ebt_rescore's meaning: 1 exact, 0 widen k', -2 / -3 as there).
+ * A row that belongs to several groups appears in each. groups[g] >= n_masks: an all-NaN / -1
+ * shelf, nothing read out of bounds. groups[g] < 0: the unfiltered list. An id may occur twice.
+ *
+ * ebt_select_topk_grouped: the streaming select of ebt_select_topk (dense form) with one
+ * candidate buffer and threshold per group in LDS. vals [B][ld] f32 (16-byte aligned,
+ * ld % 4 == 0) holds the scores of GLOBAL rows [col_begin, col_begin + n); for each of `segs`
+ * segments and each group the kprime largest entries whose bit is set in that group's mask,
+ * sorted by (value descending, index ascending), go to
+ * out_vals / out_idx[(g * B + b) * ld_out + seg * kprime + j] -- group-major, so that group g's
+ * [B][kprime] block goes straight into ebt_rescore. out_idx holds GLOBAL rows. NaN and -inf
+ * never enter; empty slots are -inf / -1, as ebt_select_topk's. One launch serves
+ * ebt_grouped_pass_groups(kprime) groups (the largest count whose buffers fit the 64 KiB of LDS
+ * the kernel asks for; >= 1 and non-increasing in kprime; 0 for a kprime out of range), so the
+ * entry runs ceil(G / that) launches and EACH LAUNCH READS vals AGAIN. Found on the host before
+ * any HIP call, EBT_EINVAL with a message that starts with the entry's name: a null pointer,
+ * G outside [1, EBT_GROUPS_MAX], kprime outside [1, EBT_GROUPED_KPRIME_MAX], words not a
+ * multiple of 4 or 32 * words < col_begin + n, n_masks < 1, ld % 4 != 0 or ld < n, B < 0,
+ * n < 0, segs outside [1, 65535], ld_out < segs * kprime. B == 0 is EBT_OK without a launch.
+ *
+ * ebt_cosine_topk_grouped_prepared takes the 24 operands every prepared entry starts with, then
+ * groups (device int32 [G]), G, the table, a workspace of ebt_cosine_topk_grouped_workspace(B,
+ * B_pad, n_rows, kprime, chunk_rows, flags, G) bytes (EBT_ENOMEM when smaller; the sizing returns
+ * 0 for arguments out of range), out_scores f64 [G][B][k], out_rows i64 [G][B][k], certified
+ * i32 [G][B], timer, stream. It runs the unfused path only, one score chunk at a time
+ * (ebt_screen_scores, or ebt_screen_exact under EBT_FLAG_EXACT; ebt_mask_excluded; the grouped
+ * select), then one merge of every (g, b)'s per-chunk lists (ebt_select_topk's candidate-list
+ * form over G B rows) and G rescores, one per group block. Timed under the existing stages
+ * (EBT_STAGE_GEMM, _MASK, _SELECT, _MERGE_SELECT, _RESCORE): no new timer stage.
+ * EBT_EUNSUPPORTED: min(k, n_rows) > EBT_GROUPED_KPRIME_MAX (the full-sort path included) and
+ * row_offset != 0 (a row-sharded catalog). EBT_EINVAL as ebt_cosine_topk_prepared's, plus
+ * kprime > EBT_GROUPED_KPRIME_MAX, G out of range and a bad table. */
+#define EBT_GROUPS_MAX 64
+#define EBT_GROUPED_KPRIME_MAX 512
+int32_t ebt_grouped_pass_groups(int32_t kprime);
+int ebt_select_topk_grouped(const float* vals, int64_t ld, int64_t B, int64_t n,
+                            int64_t col_begin, const uint32_t* masks, int64_t words,
+                            int32_t n_masks, const int32_t* groups, int32_t G, int32_t kprime,
+                            int32_t segs, float* out_vals, int64_t* out_idx, int64_t ld_out,
+                            void* stream);
+size_t ebt_cosine_topk_grouped_workspace(int64_t B, int64_t B_pad, int64_t n_rows, int32_t kprime,
+                                         int64_t chunk_rows, int flags, int32_t G);
+int ebt_cosine_topk_grouped_prepared(
+    const double* q64, const void* qimg, const float* qscale, const float* eps, int64_t B,
+    int64_t B_pad, const void* cat, int dtype, int64_t ld, const double* gnorm64,
+    const void* cimg, const float* cscale, int img_dtype, int32_t ld_img, int64_t n_rows,
+    int32_t d, int32_t d_pad, int64_t row_offset, const int64_t* excl_off,
+    const int64_t* excl_rows, int32_t k, int32_t kprime, int64_t chunk_rows, int flags,
+    const int32_t* groups, int32_t G, const uint32_t* masks, int64_t words, int32_t n_masks,
+    void* workspace, size_t ws_bytes, double* out_scores, int64_t* out_rows, int32_t* certified,
+    void* timer, void* stream);
 
 /* ---- two-phase top-k over a row-sharded catalog (robot_ebert_amd/distributed.py) ---------
  * Phase 1, every rank: ebt_cosine_screen = ebt_cosine_topk_prepared without the rescore: the shard's k'

@@ -31,6 +31,11 @@ row already picked); ``lib.get_user_recs_diverse`` is the recommend call over it
 the liked rows into up to c clusters, each cluster is searched on its own, and the answers are
 interleaved in proportion to the clusters' sizes; ``lib.get_user_recs_interests`` is the recommend
 call over it ("more like X", X the cluster's medoid).
+
+``score_topk_grouped`` (ABI 0.12.0) fills a front page: the top k of every query within each of G
+allow masks ("top drama for you", "top comedy for you") from ONE scoring pass, each shelf bit for
+bit what ``score_topk(..., allow=)`` returns for that mask; ``lib.get_user_recs_by_group`` is the
+recommend call over it.
 """
 from ._lib import EbertError, Timer, load  # noqa: F401
 from .catalog import Catalog  # noqa: F401
@@ -41,6 +46,7 @@ from .explain import Explanation, explain_topk  # noqa: F401
 from .diversify import Diversified, diversify_topk  # noqa: F401
 from .interests import (Interests, MultiInterest, cluster_liked,  # noqa: F401
                         multi_interest_topk)
+from .grouped import GroupedTopk, score_topk_grouped  # noqa: F401
 from . import ops  # noqa: F401,E402  (registers torch.ops.ebert.*)
 
 __version__ = "0.1.0"

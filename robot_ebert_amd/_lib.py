@@ -31,6 +31,8 @@ EBT_MMR_POOL_MAX = 512       # ebert.h: the largest candidate pool of ebt_pool_g
 EBT_INTEREST_MAX = 8         # ebert.h: the most clusters of ebt_interest_cluster / _interleave
 EBT_INTEREST_ITERS = 16      # ebert.h: the reassignment passes of ebt_interest_cluster
 EBT_INTEREST_K_MAX = 512     # ebert.h: the largest k of ebt_interest_interleave
+EBT_GROUPS_MAX = 64          # ebert.h: the most groups of one ebt_select_topk_grouped call
+EBT_GROUPED_KPRIME_MAX = 512 # ebert.h: the largest k' (and min(k, n)) of the grouped entries
 
 
 class EbertError(RuntimeError):
@@ -164,6 +166,14 @@ _SIGNATURES = {
                              _VP], _INT),
     "ebt_interest_interleave": ([_VP, _VP, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP],
                                 _INT),
+    "ebt_grouped_pass_groups": ([_I32], _I32),
+    "ebt_select_topk_grouped": ([_VP, _I64, _I64, _I64, _I64, _VP, _I64, _I32, _VP, _I32, _I32,
+                                 _I32, _VP, _VP, _I64, _VP], _INT),
+    "ebt_cosine_topk_grouped_workspace": ([_I64, _I64, _I64, _I32, _I64, _INT, _I32], _SZ),
+    "ebt_cosine_topk_grouped_prepared": ([_VP, _VP, _VP, _VP, _I64, _I64, _VP, _INT, _I64, _VP,
+                                          _VP, _VP, _INT, _I32, _I64, _I32, _I32, _I64, _VP, _VP,
+                                          _I32, _I32, _I64, _INT, _VP, _I32, _VP, _I64, _I32,
+                                          _VP, _SZ, _VP, _VP, _VP, _VP, _VP], _INT),
     "ebt_sharded_workspace_bytes": ([_PCAT, _PCOMM, _I64, _I32, _POPT], _SZ),
     "ebt_cosine_topk_sharded": ([_PCAT, _PCOMM, _VP, _INT, _I64, _I64, _VP, _VP, _I32, _VP, _VP,
                                  _POPT, _VP, _SZ, _VP, _VP, _VP, _VP], _INT),

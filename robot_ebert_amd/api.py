@@ -11,7 +11,7 @@ reference's other routers (movies, search, login) are out of scope.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import Dict, List, Optional
 
 from fastapi import APIRouter, FastAPI, Query
 
@@ -60,6 +60,17 @@ def get_user_recommendations_interests(user_id: str, k: int = 10,
     proportion to the clusters' sizes, each with the cluster's most central liked movie as its
     anchor (no counterpart in the reference; never batched)"""
     return lib.get_user_recs_interests(user_id=user_id, k=k, interests=interests)
+
+
+@router.get("/users/{user_id}/recommendations/by-group/")
+def get_user_recommendations_by_group(user_id: str, k: int = 10,
+                                      groups: Optional[str] = None
+                                      ) -> Dict[str, List[Recommendation]]:
+    """one shelf of k recommendations per group ("top drama for you"): `groups` is a
+    comma-separated list of mask names or indices of the configured allow masks (default: every
+    mask), all shelves scored in one pass (no counterpart in the reference; never batched)"""
+    names = [g.strip() for g in groups.split(",") if g.strip()] if groups is not None else None
+    return lib.get_user_recs_by_group(user_id=user_id, k=k, groups=names)
 
 
 def app(batcher=None) -> FastAPI:

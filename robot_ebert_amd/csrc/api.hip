@@ -626,7 +626,7 @@ using namespace ebt;
 
 extern "C" {
 
-int ebt_version(void) { return 1100; }  // 0.11.0: multi-interest top-k, cluster + interleave (ebert.h)
+int ebt_version(void) { return 1200; }  // 0.12.0: grouped top-k, one list per (query, group) (ebert.h)
 
 const char* ebt_last_error(void) { return g_err; }
 

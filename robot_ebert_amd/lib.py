@@ -12,7 +12,7 @@ set with ``configure``.
 """
 from __future__ import annotations
 
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
@@ -361,6 +361,53 @@ def get_user_recs_interests(user_id: str, k: int = 10,
     return [InterestRecommendation(movie=movies[t], score=sc, interest=cl,
                                    anchor_tmdb_id=anchor[cl])
             for t, sc, cl in items if t in movies]
+
+
+def _shelf_groups(masks, groups) -> List[Tuple[str, object]]:
+    """(shelf key, group) of every requested shelf: every mask of the table when ``groups`` is
+    None, keyed by its name (or its index as a string when the masks have no names). A string
+    that is no mask name but reads as an integer is an index."""
+    if groups is None:
+        return [(str(masks.names[m]) if masks.names is not None else str(m), m)
+                for m in range(masks.n_masks)]
+    out = []
+    for g in groups:
+        if isinstance(g, str) and (masks.names is None or g not in masks.names) \
+                and g.strip().lstrip("-").isdigit():
+            out.append((g.strip(), int(g)))
+        else:
+            out.append((str(g), g))
+    return out
+
+
+def get_user_recs_by_group(user_id: str, k: int = 10, groups=None,
+                           masks=None) -> Dict[str, List[Recommendation]]:
+    """``get_user_recs`` once per shelf of a front page ("top drama for you", "top comedy for
+    you"): the same SQL, liked / rated sets, errors (``{}`` for a user without ratings, sklearn's
+    ValueError for one without a liked movie) and hydration (lib.py:55-63) per shelf, but all the
+    shelves come from ONE scoring pass (``grouped.score_topk_grouped``). Shelf ``g`` holds what
+    ``get_user_recs(user_id, k, allow=g)`` returns.
+
+    groups: mask names or indices of ``masks`` (default: every mask); masks: an
+    ``allow.AllowMasks`` over the catalog (default: the configured ``allow_masks``). The result
+    is keyed by the group as it was asked for (a name, or the index as a string), in that order.
+    A movie of several genres appears on each of its shelves. A row-sharded catalog raises
+    EbertError."""
+    from ._lib import EbertError
+    from .grouped import resolve_groups, score_topk_grouped
+    masks = masks if masks is not None else allow_masks
+    if masks is None:
+        raise EbertError("get_user_recs_by_group needs lib.configure(allow_masks=...) or masks=")
+    shelves = _shelf_groups(masks, groups)
+    resolve_groups(masks, [g for _, g in shelves])   # a bad name fails before the SQL
+    req = _user_request(user_id)
+    if req is None:
+        return {}
+    liked, rated = req
+    got = score_topk_grouped(movies_collab_catalog, k, masks, [g for _, g in shelves],
+                             liked=[liked], exclude=[rated])
+    s, r = got.scores[0].cpu().numpy(), got.rows[0].cpu().numpy()
+    return {key: _hydrate(s[i], r[i]) for i, (key, _) in enumerate(shelves)}
 
 
 def get_user_recs_batched(batcher, user_id: str, k: int = 10, allow=None,
