@@ -167,31 +167,28 @@ static int on_rows_dev(const Timer* t, F f) {
   return rc;
 }
 
-struct StageScope {
-  Timer* t;
-  int stage;
-  hipStream_t st;
-  hipEvent_t a = nullptr, b = nullptr;
-  StageScope(void* timer, int s, hipStream_t stream) : t((Timer*)timer), stage(s), st(stream) {
-    // an unrecorded stage adds no event (each recorded pair costs the stream ~5 us of gaps)
-    if (t && !((t->mask >> s) & 1u)) t = nullptr;
-    if (t) {
-      std::lock_guard<std::mutex> g(t->mu);
-      a = t->get();
-      b = t->get();
-      if (a) (void)hipEventRecord(a, st);
-    }
-  }
-  ~StageScope() {
-    if (t && a && b) {
-      (void)hipEventRecord(b, st);
-      std::lock_guard<std::mutex> g(t->mu);
-      t->recs.push_back({stage, a, b});
-    }
-  }
-};
-
 }  // namespace
+
+// StageScope (internal.h): the one timed-stage type of the library
+StageScope::StageScope(void* timer, int s, hipStream_t stream) : t(timer), stage(s), st(stream) {
+  Timer* tm = (Timer*)timer;
+  // an unrecorded stage adds no event (each recorded pair costs the stream ~5 us of gaps)
+  if (tm && !((tm->mask >> s) & 1u)) t = tm = nullptr;
+  if (tm) {
+    std::lock_guard<std::mutex> g(tm->mu);
+    a = tm->get();
+    b = tm->get();
+    if (a) (void)hipEventRecord(a, st);
+  }
+}
+StageScope::~StageScope() {
+  Timer* tm = (Timer*)t;
+  if (tm && a && b) {
+    (void)hipEventRecord(b, st);
+    std::lock_guard<std::mutex> g(tm->mu);
+    tm->recs.push_back({stage, a, b});
+  }
+}
 
 // A stage that is exactly one kernel launch (the filter GEMM's, the roofline's dominant kernel):
 // its event pair is handed to the launch (take_launch_events -> hipExtLaunchKernelGGL), which
@@ -252,9 +249,8 @@ struct KernelStage {
 // Fused:    the same for the HEAD rows [0, H) (chunked), plus the candidate rows
 //           [B][kprime + cap] (head top-k' then appended tail candidates), counters and
 //           thresholds. The tail rows [H, n) never materialise scores.
-struct WsLayout {
-  int64_t chunk, ld_s, n_chunks, head, seg_max, group_rows, ld_cand, ld_counts;
-  int segs;
+struct WsLayout : ChunkPlan {   // (the plan of the head rows)
+  int64_t head, seg_max, group_rows, ld_cand, ld_counts;
   bool fused, pilot;
   // speculative fused screen: `spec_tiles` 256-row sample tiles, `spec_stride` tiles apart;
   // threshold = the spec_j-th best sample score - 2 eps; ~spec_hits expected hits per query
@@ -418,6 +414,28 @@ int64_t shard_lead_tiles(int64_t B_pad, int64_t n_rows, int64_t sample_tiles) {
              ? shard_lead_room(B_pad, n_rows, sample_tiles) : 0;
 }
 
+// The unfused path's plan for `rows` catalog rows (ws_layout's head, the grouped pipeline's
+// catalog): the only copy of the chunk, pitch and segment rules.
+ChunkPlan chunk_plan(int64_t B, int64_t rows, int64_t chunk_rows) {
+  ChunkPlan P{};
+  P.chunk = chunk_rows < rows ? chunk_rows : rows;
+  if (P.chunk < 1) P.chunk = 1;
+  P.ld_s = (P.chunk + 3) & ~(int64_t)3;
+  // score rows >= 4 KiB: pitch = 64 floats past a multiple of 64, so the store epilogue's 16
+  // query rows per instruction and the select's concurrent rows do not all start on the same
+  // HBM channel (a power-of-two pitch measured 5x slower writes and reads)
+  if (P.ld_s >= 1024) P.ld_s = (P.ld_s + 63) / 64 * 64 + 64;
+  P.n_chunks = ceil_div(rows, P.chunk);
+  // enough select workgroups to fill the chip: >= 512 (2 per CU)
+  int64_t segs = B > 0 ? ceil_div(512, B) : 1;
+  int64_t max_segs = P.chunk / (2 * 4096);
+  if (max_segs < 1) max_segs = 1;
+  if (segs > max_segs) segs = max_segs;
+  if (segs < 1) segs = 1;
+  P.segs = (int)segs;
+  return P;
+}
+
 static WsLayout ws_layout(int64_t B, int64_t B_pad, int64_t n_rows, int32_t kprime,
                           int64_t chunk_rows, int flags) {
   WsLayout L{};
@@ -479,22 +497,8 @@ static WsLayout ws_layout(int64_t B, int64_t B_pad, int64_t n_rows, int32_t kpri
     const int64_t rt = round_tiles(B_pad);
     L.round_rows = rt > 1 ? rt * 256 : 0;
   }
-  L.chunk = chunk_rows < L.head ? chunk_rows : L.head;
-  if (L.spec) L.chunk = L.head / 64;  // the sample's pooled maxima (4 per tile)
-  if (L.chunk < 1) L.chunk = 1;
-  L.ld_s = (L.chunk + 3) & ~(int64_t)3;
-  // score rows >= 4 KiB: pitch = 64 floats past a multiple of 64, so the store epilogue's 16
-  // query rows per instruction and the select's concurrent rows do not all start on the same
-  // HBM channel (a power-of-two pitch measured 5x slower writes and reads)
-  if (L.ld_s >= 1024) L.ld_s = (L.ld_s + 63) / 64 * 64 + 64;
-  L.n_chunks = ceil_div(L.head, L.chunk);
-  // enough select workgroups to fill the chip: >= 512 (2 per CU)
-  int64_t segs = B > 0 ? ceil_div(512, B) : 1;
-  int64_t max_segs = L.chunk / (2 * 4096);
-  if (max_segs < 1) max_segs = 1;
-  if (segs > max_segs) segs = max_segs;
-  if (segs < 1) segs = 1;
-  L.segs = (int)segs;
+  // (the speculative screen's "chunk": the sample's pooled maxima, 4 per tile)
+  static_cast<ChunkPlan&>(L) = chunk_plan(B, L.head, L.spec ? L.head / 64 : chunk_rows);
   size_t o = 0;
   L.off_s = o;
   o = align_up(o + (size_t)B_pad * L.ld_s * 4);
@@ -538,17 +542,51 @@ static WsLayout ws_layout(int64_t B, int64_t B_pad, int64_t n_rows, int32_t kpri
   return L;
 }
 
+// One chunk of the unfused screen: the approximate scores of catalog rows [c0, c0 + nc) (local
+// rows of a.c) for every query into S (pitch ld_s), by the screening GEMM or, with EBT_FLAG_EXACT,
+// the float64 screen of the rows themselves; then -inf over what a query may not see: its
+// excluded rows and, with a.allow, the rows outside its allow mask (allow_mask.hip).
+int score_chunk(const PipeArgs& a, int64_t c0, int64_t nc, float* S, int64_t ld_s, void* timer,
+                hipStream_t st) {
+  const QueryOps& q = a.q;
+  const CatOps& c = a.c;
+  int rc;
+  {
+    StageScope s(timer, EBT_STAGE_GEMM, st);
+    if (a.flags & EBT_FLAG_EXACT) {
+      rc = screen_exact(q.q64, q.B, c.d, (const char*)c.cat + c0 * c.ld * dtype_size(c.dtype),
+                        c.dtype, c.ld, c.gnorm64 + c0, nc, S, ld_s, st);
+    } else {
+      rc = screen_gemm(q.qimg, q.B_pad, (const char*)c.cimg + c0 * c.ld_img * 2, nc, c.d_pad,
+                       c.ld_img, c.img_dtype, q.qscale, c.cscale ? c.cscale + c0 : nullptr, S,
+                       ld_s, st);
+    }
+  }
+  if (rc || !(a.excl.off || a.allow)) return rc;
+  const int64_t g0 = c.row_offset + c0;   // the masks hold GLOBAL rows
+  StageScope s(timer, EBT_STAGE_MASK, st);
+  if (a.excl.off) rc = mask_excluded(S, ld_s, q.B, g0, g0 + nc, a.excl.off, a.excl.rows, st);
+  if (!rc && a.allow) rc = mask_allowed(S, ld_s, q.B, g0, g0 + nc, a.allow, st);
+  return rc;
+}
+
+// The float64 screen's bound in place of the caller's eps: xeps[0, B) = EBT_EXACT_EPS
+int fill_exact_eps(float* xeps, int64_t B, hipStream_t st) {
+  const float e = EBT_EXACT_EPS;
+  uint32_t bits;
+  memcpy(&bits, &e, 4);
+  return hip_check(hipMemsetD32Async((hipDeviceptr_t)xeps, (int)bits, (size_t)B, st),
+                   "hipMemsetD32Async");
+}
+
 // Top-k' of rows [r0, r0+nrows) of the (shard-local) catalog into dv/di (row stride ld_d), the
 // unfused way: chunked GEMM (EBT_FLAG_EXACT: the float64 screen of the catalog rows themselves)
 // -> mask -> streaming select (-> select across chunks).
 static int head_topk(const PipeArgs& a, const WsLayout& L, char* ws, int64_t r0, int64_t nrows,
                      float* dv_final, int64_t* di_final, int64_t ld_final, void* timer,
                      hipStream_t st) {
-  const QueryOps& q = a.q;
-  const CatOps& c = a.c;
-  const int64_t B = q.B, row_offset = c.row_offset;
+  const int64_t B = a.q.B;
   const int32_t kprime = a.kprime;
-  const bool exact = a.flags & EBT_FLAG_EXACT;
   float* S = (float*)(ws + L.off_s);
   float* segv = (float*)(ws + L.off_segv);
   int64_t* segi = (int64_t*)(ws + L.off_segi);
@@ -559,29 +597,8 @@ static int head_topk(const PipeArgs& a, const WsLayout& L, char* ws, int64_t r0,
   for (int64_t ch = 0; ch < n_chunks; ++ch) {
     const int64_t c0 = r0 + ch * L.chunk;
     const int64_t nc = (r0 + nrows - c0) < L.chunk ? (r0 + nrows - c0) : L.chunk;
-    {
-      StageScope s(timer, EBT_STAGE_GEMM, st);
-      if (exact) {
-        rc = screen_exact(q.q64, B, c.d, (const char*)c.cat + c0 * c.ld * dtype_size(c.dtype),
-                          c.dtype, c.ld,
-                          c.gnorm64 + c0, nc, S, L.ld_s, st);
-      } else {
-        rc = screen_gemm(q.qimg, q.B_pad, (const char*)c.cimg + c0 * c.ld_img * 2, nc, c.d_pad,
-                         c.ld_img, c.img_dtype, q.qscale, c.cscale ? c.cscale + c0 : nullptr, S,
-                         L.ld_s, st);
-      }
-    }
+    rc = score_chunk(a, c0, nc, S, L.ld_s, timer, st);
     if (rc) return rc;
-    if (a.excl.off || a.allow) {
-      StageScope s(timer, EBT_STAGE_MASK, st);
-      rc = a.excl.off ? mask_excluded(S, L.ld_s, B, row_offset + c0, row_offset + c0 + nc,
-                                      a.excl.off, a.excl.rows, st)
-                      : EBT_OK;
-      // per-query allow masks (allow_mask.hip): the rows a filtered query may not see
-      if (!rc && a.allow)
-        rc = mask_allowed(S, L.ld_s, B, row_offset + c0, row_offset + c0 + nc, a.allow, st);
-      if (rc) return rc;
-    }
     float* dv = n_chunks == 1 ? dv_final : chv + ch * kprime;
     int64_t* di = n_chunks == 1 ? di_final : chi + ch * kprime;
     const int64_t ld_d = n_chunks == 1 ? ld_final : n_chunks * kprime;
@@ -1066,11 +1083,7 @@ static int run_screen(const PipeArgs& a, const WsLayout& L, char* ws, float* fv,
   const int32_t k = a.k, kprime = a.kprime;
   if (a.flags & EBT_FLAG_EXACT) {  // float64 screen; its bound replaces the caller's eps
     float* xeps = (float*)(ws + L.off_eps);
-    const float e = EBT_EXACT_EPS;
-    uint32_t bits;
-    memcpy(&bits, &e, 4);
-    rc = hip_check(hipMemsetD32Async((hipDeviceptr_t)xeps, (int)bits, (size_t)B, st),
-                   "hipMemsetD32Async");
+    rc = fill_exact_eps(xeps, B, st);
     if (rc) return rc;
     so->eps = xeps;
     return head_topk(a, L, ws, 0, n_rows, fv, fi, kprime, timer, st);
@@ -1083,18 +1096,10 @@ static int run_screen(const PipeArgs& a, const WsLayout& L, char* ws, float* fv,
   // 1. head rows [0, H): exact top-k' per query (the list fv/fi)
   if (L.pilot) {
     float* S = (float*)(ws + L.off_s);
-    {
-      StageScope s(timer, EBT_STAGE_GEMM, st);
-      rc = screen_gemm(q.qimg, B_pad, c.cimg, L.head, c.d_pad, c.ld_img, c.img_dtype, q.qscale,
-                       c.cscale, S, L.ld_s, st);
-    }
+    // (a.allow is null here: topk_prepared sets EBT_FLAG_NO_FUSE for a filtered batch, and the
+    // pilot is the fused screen's head, so the step masks the exclusions only)
+    rc = score_chunk(a, 0, L.head, S, L.ld_s, timer, st);
     if (rc) return rc;
-    if (a.excl.off) {
-      StageScope s(timer, EBT_STAGE_MASK, st);
-      rc = mask_excluded(S, L.ld_s, B, row_offset, row_offset + L.head, a.excl.off, a.excl.rows,
-                         st);
-      if (rc) return rc;
-    }
     StageScope s(timer, EBT_STAGE_SELECT, st);
     rc = pilot_topk(S, L.ld_s, B, (int)L.head, 0, kprime, k, fv, fi, st);
   } else {

@@ -25,14 +25,13 @@
 //    The buffers of all G groups do not fit in LDS at large G k': a launch serves
 //    ebt_grouped_pass_groups(k') groups and the entry runs ceil(G / that) launches. EACH LAUNCH
 //    READS THE SCORE CHUNK AGAIN (B n 4 bytes).
-//  * ebt_cosine_topk_grouped_prepared -- the unfused pipeline around it: per chunk screen, mask
-//    the excluded rows, grouped select; then one merge of every (group, query)'s per-chunk lists
+//  * ebt_cosine_topk_grouped_prepared -- the unfused pipeline around it, on the unfused path's own
+//    plan and chunk step (api.hip chunk_plan, score_chunk): per chunk screen, mask the excluded
+//    rows, grouped select; then one merge of every (group, query)'s per-chunk lists
 //    (ebt_select_topk's candidate-list form over G B rows) and G rescores, one per group block.
 //    Group g's block sees the approximate scores, the selection rule and the rescore that
 //    ebt_cosine_topk_prepared_allowed gives a batch whose queries all carry mask groups[g], so
 //    its scores, rows and certificates are that call's.
-#include <cstring>
-
 #include "common.h"
 #include "internal.h"
 #include "select_core.h"
@@ -358,19 +357,6 @@ __global__ __launch_bounds__(STHREADS, 2) void grouped_select_kernel(const Group
   }
 }
 
-// A timed stage around launches made through other entries (api.hip's StageScope is local to it)
-struct Stage {
-  void* timer;
-  int stage;
-  void* st;
-  Stage(void* t, int s, void* stream) : timer(t), stage(s), st(stream) {
-    if (timer) (void)ebt_timer_begin(timer, stage, st);
-  }
-  ~Stage() {
-    if (timer) (void)ebt_timer_end(timer, stage, st);
-  }
-};
-
 int check_table(const char* who, const uint32_t* masks, int64_t words, int32_t n_masks,
                 int64_t row_end) {
   if (words < 1 || words % 4 != 0 || n_masks < 1 || words > (INT64_MAX >> 5) ||
@@ -428,27 +414,16 @@ int select_grouped(const float* vals, int64_t ld, int64_t B, int64_t n, int64_t 
 // The workspace of ebt_cosine_topk_grouped_prepared:
 //   [S: B_pad x ld_s f32][per-chunk, per-segment lists of G B rows][final lists of G B rows]
 //   [eps B_pad, the float64 screen only]
-struct GroupedWs {
-  int64_t chunk, ld_s, n_chunks, lists;   // lists = n_chunks * segs per (group, query)
-  int segs;
+struct GroupedWs : ChunkPlan {   // (the unfused path's plan of the whole catalog)
+  int64_t lists;                 // n_chunks * segs per (group, query)
   size_t off_s, off_lv, off_li, off_fv, off_fi, off_eps, bytes;
 };
 
 GroupedWs grouped_ws(int64_t B, int64_t B_pad, int64_t n_rows, int32_t kprime, int64_t chunk_rows,
                      int flags, int32_t G) {
   GroupedWs L{};
-  // the chunking, the score pitch and the segments of the unfused path (api.hip ws_layout), so
-  // that every chunk goes through the screening GEMM exactly as it does there
-  L.chunk = chunk_rows < n_rows ? chunk_rows : n_rows;
-  if (L.chunk < 1) L.chunk = 1;
-  L.ld_s = (L.chunk + 3) & ~(int64_t)3;
-  if (L.ld_s >= 1024) L.ld_s = (L.ld_s + 63) / 64 * 64 + 64;
-  L.n_chunks = ceil_div(n_rows, L.chunk);
-  int64_t segs = B > 0 ? ceil_div(512, B) : 1;
-  int64_t max_segs = L.chunk / (2 * 4096);
-  if (max_segs < 1) max_segs = 1;
-  if (segs > max_segs) segs = max_segs;
-  L.segs = (int)(segs < 1 ? 1 : segs);
+  // so that every chunk goes through the screening GEMM exactly as it does on the unfused path
+  static_cast<ChunkPlan&>(L) = chunk_plan(B, n_rows, chunk_rows);
   L.lists = L.n_chunks * L.segs;
   const size_t rows = (size_t)G * (size_t)B;
   size_t o = 0;
@@ -542,6 +517,10 @@ int ebt_cosine_topk_grouped_prepared(
     return EBT_ENOMEM;
   }
   hipStream_t st = (hipStream_t)stream;
+  const PipeArgs a{{q64, qimg, qscale, eps, B, B_pad},
+                   {cat, dtype, ld, gnorm64, cimg, cscale, img_dtype, ld_img, n_rows, d, d_pad,
+                    row_offset},
+                   {excl_off, excl_rows}, k, kprime, chunk_rows, flags};
   char* ws = (char*)workspace;
   float* S = (float*)(ws + L.off_s);
   float* fv = (float*)(ws + L.off_fv);
@@ -550,52 +529,33 @@ int ebt_cosine_topk_grouped_prepared(
   int64_t* li = L.lists > 1 ? (int64_t*)(ws + L.off_li) : fi;
   const int64_t ld_l = L.lists * kprime;
   const float* eps_use = eps;
-  if (exact) {  // the float64 screen's bound replaces the caller's eps (api.hip run_screen)
+  if (exact) {  // the float64 screen's bound replaces the caller's eps
     float* xeps = (float*)(ws + L.off_eps);
-    const float e = EBT_EXACT_EPS;
-    uint32_t bits;
-    memcpy(&bits, &e, 4);
-    rc = hip_check(hipMemsetD32Async((hipDeviceptr_t)xeps, (int)bits, (size_t)B, st),
-                   "hipMemsetD32Async");
+    rc = fill_exact_eps(xeps, B, st);
     if (rc) return rc;
     eps_use = xeps;
   }
   for (int64_t ch = 0; ch < L.n_chunks; ++ch) {
     const int64_t c0 = ch * L.chunk;
     const int64_t nc = n_rows - c0 < L.chunk ? n_rows - c0 : L.chunk;
-    {
-      Stage s(timer, EBT_STAGE_GEMM, stream);
-      if (exact) {
-        rc = screen_exact(q64, B, d, (const char*)cat + c0 * ld * dtype_size(dtype), dtype, ld,
-                          gnorm64 + c0, nc, S, L.ld_s, st);
-      } else {
-        rc = screen_gemm(qimg, B_pad, (const char*)cimg + c0 * ld_img * 2, nc, d_pad, ld_img,
-                         img_dtype, qscale, cscale ? cscale + c0 : nullptr, S, L.ld_s, st);
-      }
-    }
+    rc = score_chunk(a, c0, nc, S, L.ld_s, timer, st);
     if (rc) return rc;
-    if (excl_off) {
-      Stage s(timer, EBT_STAGE_MASK, stream);
-      rc = mask_excluded(S, L.ld_s, B, c0, c0 + nc, excl_off, excl_rows, st);
-      if (rc) return rc;
-    }
-    Stage s(timer, EBT_STAGE_SELECT, stream);
+    StageScope s(timer, EBT_STAGE_SELECT, st);
     rc = select_grouped(S, L.ld_s, B, nc, c0, masks, words, n_masks, groups, G, kprime, L.segs,
                         lv + ch * L.segs * kprime, li + ch * L.segs * kprime, ld_l, st);
     if (rc) return rc;
   }
   if (L.lists > 1) {  // every (group, query)'s per-chunk, per-segment lists -> its k' best
-    Stage s(timer, EBT_STAGE_MERGE_SELECT, stream);
+    StageScope s(timer, EBT_STAGE_MERGE_SELECT, st);
     rc = select_topk(lv, li, ld_l, (int64_t)G * B, ld_l, 0, kprime, 1, fv, fi, kprime, st);
     if (rc) return rc;
   }
-  const CatOps c{cat, dtype, ld, gnorm64, cimg, cscale, img_dtype, ld_img, n_rows, d, d_pad, 0};
-  Stage s(timer, EBT_STAGE_RESCORE, stream);
+  StageScope s(timer, EBT_STAGE_RESCORE, st);
   for (int32_t g = 0; g < G; ++g) {
     const int64_t o = (int64_t)g * B;
-    rc = rescore(q64, B, c, {fv + o * kprime, fi + o * kprime, kprime, 0}, k, eps_use, nullptr,
+    rc = rescore(q64, B, a.c, {fv + o * kprime, fi + o * kprime, kprime, 0}, k, eps_use, nullptr,
                  out_scores + o * k, out_rows + o * k, certified + o,
-                 {nullptr, nullptr, {excl_off, excl_rows}, nullptr, nullptr}, st);
+                 {nullptr, nullptr, a.excl, nullptr, nullptr}, st);
     if (rc) return rc;
   }
   return EBT_OK;

@@ -12,8 +12,11 @@
 //     and linkage, so that kernel symbols do not change; its name is unique in the library.
 //   * A type shared by two files is defined in exactly one header (common.h, here, driver.h) under
 //     a name that no .hip file defines. Here: the operand records QueryOps, CatOps, ExclCsr,
-//     HitSlots, LeadIn, GatheredSamples, PipeArgs, WaveMergeOpts, CandList, RescoreExtras --
-//     host-only aggregates, filled by name at the one place where positional arguments come in.
+//     HitSlots, LeadIn, GatheredSamples, PipeArgs, WaveMergeOpts, CandList, RescoreExtras and
+//     the unfused path's ChunkPlan -- host-only aggregates, filled by name at the one place where
+//     positional arguments come in -- and StageScope, the timed stage of every file: its
+//     constructor and destructor are api.hip's, where the timer behind its handle (Timer) stays
+//     file-local, as do KernelStage and WsLayout.
 //   * A function with external linkage is declared in common.h, here, or in driver.h.
 #pragma once
 
@@ -96,7 +99,34 @@ struct RescoreExtras {
   const ShardPackOut* pack; unsigned long long* gathered;
 };
 
+// The unfused path's plan for a run of catalog rows: `n_chunks` chunks of `chunk` rows, each
+// scored into a [B_pad][ld_s] block and selected from in `segs` segments per query
+struct ChunkPlan {
+  int64_t chunk, ld_s, n_chunks;
+  int segs;
+};
+
+// A timed stage: what is enqueued on `stream` during the scope's life is one record of `stage` in
+// the timer (ebt_timer_create's handle; null, or a stage outside its mask: nothing is recorded).
+// Scopes nest and repeat freely, and every way out of the block closes the stage.
+struct StageScope {
+  void* t;
+  int stage;
+  hipStream_t st;
+  hipEvent_t a = nullptr, b = nullptr;
+  StageScope(void* timer, int s, hipStream_t stream);
+  ~StageScope();
+  StageScope(const StageScope&) = delete;
+  StageScope& operator=(const StageScope&) = delete;
+};
+
 // ---- api.hip ---------------------------------------------------------------------------------
+ChunkPlan chunk_plan(int64_t B, int64_t rows, int64_t chunk_rows);
+// rows [c0, c0 + nc) of a.c scored into S (pitch ld_s) under the GEMM stage, then a.excl and
+// a.allow applied under one MASK stage (opened only if one of them is set)
+int score_chunk(const PipeArgs& a, int64_t c0, int64_t nc, float* S, int64_t ld_s, void* timer,
+                hipStream_t st);
+int fill_exact_eps(float* xeps, int64_t B, hipStream_t st);
 int64_t shard_lead_room(int64_t B_pad, int64_t n_rows, int64_t sample_tiles);
 int64_t shard_lead_tiles(int64_t B_pad, int64_t n_rows, int64_t sample_tiles);
 // x.gathered is taken from the timer

@@ -168,9 +168,11 @@ unsigned grid_for(int64_t total) {
 
 int sh_gather(const ebt_comm& cm, const void* send, void* recv, size_t bytes, void* timer,
               hipStream_t st) {
-  if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_COLLECTIVE, st);
-  const int rc = cm.all_gather(cm.ctx, send, recv, bytes, (void*)st);
-  if (timer) (void)ebt_timer_end(timer, EBT_STAGE_COLLECTIVE, st);
+  int rc;
+  {
+    StageScope s(timer, EBT_STAGE_COLLECTIVE, st);
+    rc = cm.all_gather(cm.ctx, send, recv, bytes, (void*)st);
+  }
   if (rc) {
     set_error("ebt_cosine_topk_sharded: the caller's all_gather returned %d", rc);
     return EBT_EHIP;
@@ -197,9 +199,11 @@ int prep_liked_sharded(const ebt_catalog& c, const ebt_comm& cm, const int64_t* 
                            c.row_offset, c.n);
   if (rc) return rc;
   if (cm.all_reduce_f64) {  // the caller's all-reduce (RCCL: about 2 / R of the gather's bytes)
-    if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_COLLECTIVE, st);
-    const int e = cm.all_reduce_f64(cm.ctx, q64, (size_t)B * c.d, (void*)st);
-    if (timer) (void)ebt_timer_end(timer, EBT_STAGE_COLLECTIVE, st);
+    int e;
+    {
+      StageScope s(timer, EBT_STAGE_COLLECTIVE, st);
+      e = cm.all_reduce_f64(cm.ctx, q64, (size_t)B * c.d, (void*)st);
+    }
     if (e) {
       set_error("ebt_cosine_topk_sharded: the caller's all_reduce_f64 returned %d", e);
       return EBT_EHIP;
@@ -228,10 +232,8 @@ int sh_full_merge(const ShardLayout& S, const ebt_comm& cm, char* ws, int64_t B,
   int rc = sh_gather(cm, ls, gs, (size_t)B * k * 8, timer, st);
   if (!rc) rc = sh_gather(cm, lrr, gr, (size_t)B * k * 8, timer, st);
   if (rc) return rc;
-  if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_SHARD_MERGE, st);
-  rc = ebt_merge_topk(gs, gr, cm.world, B, k, out_s, out_r, st);
-  if (timer) (void)ebt_timer_end(timer, EBT_STAGE_SHARD_MERGE, st);
-  return rc;
+  StageScope s(timer, EBT_STAGE_SHARD_MERGE, st);
+  return ebt_merge_topk(gs, gr, cm.world, B, k, out_s, out_r, st);
 }
 }  // namespace
 }  // namespace ebt
@@ -295,11 +297,13 @@ int ebt_cosine_topk_sharded_weighted_submit(
   const float* qeps = (const float*)(prep + L.prep.eps);
   int rc = EBT_OK;
   // 1. the queries (lib.py:51-52)
-  if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_PREP, st);
-  rc = q ? prep_dense(c, q, q_dtype, B, ldq, L.prep, prep, st)
-         : prep_liked_sharded(c, cm, liked_off, liked_rows, liked_w, B, L.prep, prep,
-                              (double*)(ws + S.off_scale), (double*)(ws + S.off_qrecv), timer, st);
-  if (timer) (void)ebt_timer_end(timer, EBT_STAGE_PREP, st);
+  {
+    StageScope s(timer, EBT_STAGE_PREP, st);
+    rc = q ? prep_dense(c, q, q_dtype, B, ldq, L.prep, prep, st)
+           : prep_liked_sharded(c, cm, liked_off, liked_rows, liked_w, B, L.prep, prep,
+                                (double*)(ws + S.off_scale), (double*)(ws + S.off_qrecv), timer,
+                                st);
+  }
   if (rc) return rc;
   // 2. the catalog-wide screening threshold from every shard's sample maxima (taken by the
   // screen's first launch, step 3)
@@ -329,9 +333,10 @@ int ebt_cosine_topk_sharded_weighted_submit(
     }
     float* send = gsamp;                          // [B][J + 1]
     float* recv = gsamp + (size_t)B * S.GJ;       // [R][B][J + 1]
-    if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_SMALL, st);
-    rc = ebt_floor_pack(pool, S.G, B, (int32_t)S.G, (int32_t)S.J, nullptr, send, st);
-    if (timer) (void)ebt_timer_end(timer, EBT_STAGE_SMALL, st);
+    {
+      StageScope s(timer, EBT_STAGE_SMALL, st);
+      rc = ebt_floor_pack(pool, S.G, B, (int32_t)S.G, (int32_t)S.J, nullptr, send, st);
+    }
     if (!rc) rc = sh_gather(cm, send, recv, (size_t)B * S.GJ * 4, timer, st);
     if (rc) return rc;
     const double m_total = 256.0 * (double)S.tiles * R;
@@ -383,18 +388,18 @@ int ebt_cosine_topk_sharded_weighted_submit(
   float* frecv = (float*)(ws + S.off_frecv);
   double* tfloor = (double*)(ws + S.off_tfloor);
   if (!use_theta) {
-    if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_SMALL, st);
+    StageScope s(timer, EBT_STAGE_SMALL, st);
     rc = ebt_floor_pack(lv, L.kprime, B, L.k_eff, (int32_t)S.fw, eps_p, fsend, st);
-    if (timer) (void)ebt_timer_end(timer, EBT_STAGE_SMALL, st);
   }
   if (!rc) rc = sh_gather(cm, fsend, frecv, (size_t)B * (S.fw + 1) * 4, timer, st);
   if (rc) return rc;
   // (the floor's launch also zeroes the merge's "incomplete" flag and the reserved word after
   // it: no memset launch)
   uint32_t* zero2 = (uint32_t*)(ws + S.off_incomplete);
-  if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_SMALL, st);
-  rc = union_floor(frecv, R, B, (int32_t)S.fw + 1, k, tfloor, st, zero2);
-  if (timer) (void)ebt_timer_end(timer, EBT_STAGE_SMALL, st);
+  {
+    StageScope s(timer, EBT_STAGE_SMALL, st);
+    rc = union_floor(frecv, R, B, (int32_t)S.fw + 1, k, tfloor, st, zero2);
+  }
   if (rc) return rc;
   // 5. the rescore of the rows that can enter the global top k, the certificate
   double* ls = (double*)(ws + S.off_ls);
@@ -480,23 +485,25 @@ int ebt_cosine_topk_sharded_finish(ebt_sharded_pending* p) {
     int32_t* incomplete = (int32_t*)(ws + S.off_incomplete);
     bool repack = lp.k_eff < k;
     for (int64_t b = 0; b < B && !repack; ++b) repack = lp.cert_host[b] != 1;
-    if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_SMALL, st);
-    rc = repack ? ebt_shard_pack((const double*)(ws + S.off_ls), (const int64_t*)(ws + S.off_lrr),
-                                 B, k, (const double*)(ws + S.off_tfloor), S.cap,
-                                 ws + S.off_psend, st)
-                : shard_pack_lens((const double*)(ws + S.off_ls),
-                                  (const int64_t*)(ws + S.off_lrr), B, k, S.cap,
-                                  ws + S.off_psend, st);
-    if (timer) (void)ebt_timer_end(timer, EBT_STAGE_SMALL, st);
+    {
+      StageScope s(timer, EBT_STAGE_SMALL, st);
+      rc = repack
+               ? ebt_shard_pack((const double*)(ws + S.off_ls), (const int64_t*)(ws + S.off_lrr),
+                                B, k, (const double*)(ws + S.off_tfloor), S.cap, ws + S.off_psend,
+                                st)
+               : shard_pack_lens((const double*)(ws + S.off_ls), (const int64_t*)(ws + S.off_lrr),
+                                 B, k, S.cap, ws + S.off_psend, st);
+    }
     if (!rc) rc = sh_gather(p->comm, ws + S.off_psend, ws + S.off_precv, S.pack_bytes, timer, st);
     if (rc) return rc;
-    if (timer) (void)ebt_timer_begin(timer, EBT_STAGE_SHARD_MERGE, st);
     // (the flag straight into the host buffer when it is pinned: zeroed above, only ever set
     // to 1 by the merge's stores; else the workspace's flag and one copy)
     int32_t* direct = host_mapped(p->host + B + 1);
-    rc = ebt_merge_packed(ws + S.off_precv, p->comm.world, B, k, S.cap, p->out_scores,
-                          p->out_rows, direct ? direct : incomplete, st);
-    if (timer) (void)ebt_timer_end(timer, EBT_STAGE_SHARD_MERGE, st);
+    {
+      StageScope s(timer, EBT_STAGE_SHARD_MERGE, st);
+      rc = ebt_merge_packed(ws + S.off_precv, p->comm.world, B, k, S.cap, p->out_scores,
+                            p->out_rows, direct ? direct : incomplete, st);
+    }
     if (!rc && !direct)
       rc = hip_check(hipMemcpyAsync(p->host + B + 1, incomplete, 4, hipMemcpyDeviceToHost, st),
                      "hipMemcpyAsync");

@@ -35,8 +35,8 @@ from ._lib import EbertError, call, ptr, region, stream_of
 from .catalog import Catalog
 from .search import (KPRIME_MAX, MERGE_WAVE_KMAX, _round_up, csr_from_lists,
                      csr_from_weighted_lists, csr_subset,
-                     default_kprime, merge_topk, pad_batch, pool_kth, prepare_queries, run_screen,
-                     _liked_with_weights,
+                     default_kprime, merge_topk, pad_batch, pad_topk, pool_kth, prepare_queries,
+                     run_screen, _liked_with_weights,
                      sample_maxima, score_topk, score_topk_finish, score_topk_stages,
                      score_topk_submit, spec_rank, union_floor_gathered)
 
@@ -262,11 +262,7 @@ def score_topk_sharded(catalog: Catalog, k: int, queries: Optional[torch.Tensor]
         s2, r2, c2 = _two_phase(catalog, qb.subset(bad), k_eff, kp, sub_ex, chunk_rows, timer,
                                 flags, coll)
         s[bad], r[bad], cert[bad] = s2, r2, c2
-    if k_eff < k:
-        pad_s = torch.full((qb.B, k - k_eff), float("nan"), dtype=torch.float64, device=dev)
-        pad_r = torch.full((qb.B, k - k_eff), -1, dtype=torch.int64, device=dev)
-        s, r = torch.cat([s, pad_s], 1), torch.cat([r, pad_r], 1)
-    return s, r
+    return pad_topk(s, r, k)
 
 
 def _gather_start(coll, t: torch.Tensor):

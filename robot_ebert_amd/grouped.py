@@ -25,9 +25,9 @@ from . import _lib
 from ._lib import EbertError, call, ptr, stream_of
 from .allow import AllowMasks
 from .catalog import Catalog
-from .search import (DEFAULT_SCORE_BUDGET, SortedCSR, _chunk_rows, _clamp_kprime,
-                     _liked_with_weights, _pipe_operands, _round_up, _take, _take_weights,
-                     csr_from_lists, csr_sorted, prepare_queries, score_topk)
+from .search import (DEFAULT_SCORE_BUDGET, _chunk_rows, _clamp_kprime, _liked_with_weights,
+                     _pipe_operands, _round_up, _take, _take_weights, check_certificates,
+                     exclusions_csr, pad_topk, prepare_queries, score_topk)
 
 
 class GroupedTopk(NamedTuple):
@@ -112,10 +112,7 @@ def score_topk_grouped(catalog: Catalog, k: int, masks: AllowMasks, groups,
                          f"{catalog.n}")
     # the inputs as score_topk_stages prepares them
     lk, lw = _liked_with_weights(liked, liked_weights, dev) if liked is not None else (None, None)
-    ex = None
-    if exclude is not None:
-        ex = (csr_from_lists(exclude, dev) if not isinstance(exclude, tuple)
-              else exclude if isinstance(exclude, SortedCSR) else csr_sorted(*exclude))
+    ex = exclusions_csr(exclude, dev)
     qb = prepare_queries(catalog, queries=queries, liked=lk, liked_weights=lw)
     B = qb.B
     if ex is not None and int(ex[0].numel()) != B + 1:
@@ -149,10 +146,7 @@ def score_topk_grouped(catalog: Catalog, k: int, masks: AllowMasks, groups,
              ptr(ws), int(ws.numel()), ptr(out_s[g0:g0 + ng]), ptr(out_r[g0:g0 + ng]),
              ptr(cert[g0:g0 + ng]), timer.handle if timer is not None else None, stream_of(dev))
     flat = cert.cpu()
-    if bool((flat == -3).any()):   # the rescore's check of the exclusion segments
-        raise EbertError("exclusion rows must be sorted ascending within each query")
-    if bool((flat == -2).any()):
-        raise EbertError("internal error: candidate row out of range (libebert bug)")
+    check_certificates(flat)
     bad = torch.nonzero(flat != 1)   # [(g, b)]: the candidate set is not provably complete
     fallback = int(bad.shape[0])
     if fallback:
@@ -169,9 +163,6 @@ def score_topk_grouped(catalog: Catalog, k: int, masks: AllowMasks, groups,
         at = (torch.tensor(gs, dtype=torch.int64, device=dev), idx)
         out_s[at] = s2
         out_r[at] = r2
-    if k_eff < k:
-        pad_s = torch.full((G, B, k - k_eff), float("nan"), dtype=torch.float64, device=dev)
-        pad_r = torch.full((G, B, k - k_eff), -1, dtype=torch.int64, device=dev)
-        out_s, out_r = torch.cat([out_s, pad_s], 2), torch.cat([out_r, pad_r], 2)
+    out_s, out_r = pad_topk(out_s, out_r, k)
     return GroupedTopk(out_s.permute(1, 0, 2).contiguous(), out_r.permute(1, 0, 2).contiguous(),
                        gid, fallback)

@@ -239,6 +239,36 @@ def csr_sorted(off, rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, 
     return SortedCSR(off, out)
 
 
+def exclusions_csr(exclude, dev) -> Optional[SortedCSR]:
+    """``exclude=`` as score_topk takes it -- None, per-query host lists, a device CSR pair or a
+    SortedCSR (used as it is) -- as a device CSR with every segment sorted ascending."""
+    if exclude is None:
+        return None
+    if not isinstance(exclude, tuple):
+        return csr_from_lists(exclude, dev)
+    return exclude if isinstance(exclude, SortedCSR) else csr_sorted(*exclude)
+
+
+def check_certificates(flat: torch.Tensor) -> None:
+    """Raise on the rescore's two certificates that no retry answers (flat: on the host)."""
+    if bool((flat == -3).any()):   # the rescore's check of the exclusion segments
+        raise EbertError("exclusion rows must be sorted ascending within each query")
+    if bool((flat == -2).any()):
+        raise EbertError("internal error: candidate row out of range (libebert bug)")
+
+
+def pad_topk(s: torch.Tensor, r: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(scores [..., k_eff], rows [..., k_eff]) of a catalog with k_eff < k rows, padded along the
+    last axis to k with NaN / -1 (as they are when k_eff == k)."""
+    k_eff = int(s.shape[-1])
+    if k_eff >= k:
+        return s, r
+    shape = (*s.shape[:-1], k - k_eff)
+    pad_s = torch.full(shape, float("nan"), dtype=torch.float64, device=s.device)
+    pad_r = torch.full(shape, -1, dtype=torch.int64, device=s.device)
+    return torch.cat([s, pad_s], -1), torch.cat([r, pad_r], -1)
+
+
 def csr_subset(off: torch.Tensor, rows: torch.Tensor, idx: torch.Tensor):
     """Rows `idx` of a device CSR (torch ops only; used for the certification retry)."""
     starts = off.index_select(0, idx)
@@ -656,9 +686,7 @@ def _submit_c(catalog: Catalog, k: int, queries, liked, exclude, kprime, chunk_r
     lw = None
     if liked_weights is not None:
         liked, lw = _liked_with_weights(liked, liked_weights, dev)
-    if exclude is not None:
-        exclude = (csr_from_lists(exclude, dev) if not isinstance(exclude, tuple)
-                   else exclude if isinstance(exclude, SortedCSR) else csr_sorted(*exclude))
+    exclude = exclusions_csr(exclude, dev)
     q_ptr, q_dt, ldq, lo, lr, lo_csr = None, 0, 0, None, None, None
     if queries is not None:
         queries = _dense_queries(queries, catalog.d)
@@ -911,9 +939,7 @@ def score_topk_stages(catalog: Catalog, k: int, queries: Optional[torch.Tensor] 
         raise EbertError("liked_wsum= goes with liked_weights=")
     if liked is not None and not isinstance(liked, tuple):
         liked = csr_from_lists(liked, dev)
-    if exclude is not None:
-        exclude = (csr_from_lists(exclude, dev) if not isinstance(exclude, tuple)
-                   else exclude if isinstance(exclude, SortedCSR) else csr_sorted(*exclude))
+    exclude = exclusions_csr(exclude, dev)
     if theta_hook is not None and t_floor_hook is None:
         raise EbertError("theta_hook needs t_floor_hook (the threshold is verified against it)")
     with region(timer, "prep", dev):
@@ -965,10 +991,7 @@ def score_topk_finish(p) -> Tuple[torch.Tensor, torch.Tensor]:
     while True:
         if flat is None:
             flat = cert.cpu()
-        if bool((flat == -3).any()):   # the rescore's check of the exclusion segments
-            raise EbertError("exclusion rows must be sorted ascending within each query")
-        if bool((flat == -2).any()):
-            raise EbertError("internal error: candidate row out of range (libebert bug)")
+        check_certificates(flat)
         over = torch.nonzero(flat == -1).flatten().to(dev)
         bad = torch.nonzero(flat == 0).flatten().to(dev)
         if over.numel() == 0 and bad.numel() == 0:
@@ -996,11 +1019,7 @@ def score_topk_finish(p) -> Tuple[torch.Tensor, torch.Tensor]:
         s2, r2, c2 = run_pipeline(catalog, qb.subset(bad), k_eff, kp, sub_ex, chunk_rows, timer,
                                   flags=flags)
         s[bad], r[bad], cert[bad] = s2, r2, c2
-    if k_eff < k:
-        pad_s = torch.full((qb.B, k - k_eff), float("nan"), dtype=torch.float64, device=dev)
-        pad_r = torch.full((qb.B, k - k_eff), -1, dtype=torch.int64, device=dev)
-        s, r = torch.cat([s, pad_s], 1), torch.cat([r, pad_r], 1)
-    return s, r
+    return pad_topk(s, r, k)
 
 
 def score_topk(catalog: Catalog, k: int, queries: Optional[torch.Tensor] = None,

@@ -240,7 +240,7 @@ def test_zero_norm_row_inside_a_group(cuda_device):
 
 
 # ---- 3. nothing hides behind the fallback -------------------------------------------------------
-def _first_pass(cat, masks, qb, ids, k, kp, chunk, excl, dev):
+def _first_pass(cat, masks, qb, ids, k, kp, chunk, excl, dev, timer=None):
     """ebt_cosine_topk_grouped_prepared alone: (scores, rows, certified), each [G, B, ...]."""
     from robot_ebert_amd import _lib, search
     lib = _lib.load()
@@ -254,7 +254,8 @@ def _first_pass(cat, masks, qb, ids, k, kp, chunk, excl, dev):
     _lib.call("ebt_cosine_topk_grouped_prepared",
               *search._pipe_operands(cat, qb, excl, k, kp, chunk, 0), gid.data_ptr(), G,
               masks.table.data_ptr(), masks.words, masks.n_masks, ws.data_ptr(), need,
-              s.data_ptr(), r.data_ptr(), c.data_ptr(), None, _lib.stream_of(dev))
+              s.data_ptr(), r.data_ptr(), c.data_ptr(),
+              timer.handle if timer is not None else None, _lib.stream_of(dev))
     return s, r, c
 
 
@@ -283,6 +284,42 @@ def test_first_pass_certificates_equal_the_masked_pipeline(cuda_device, kind, ch
         assert torch.equal(r[g], r2) and torch.equal(s[g].view(torch.int64), s2.view(torch.int64))
         seen |= set(c2.tolist())
     assert seen <= {0, 1} and 1 in seen
+
+
+@pytest.mark.parametrize("chunk,launches", [
+    (128, {"gemm": 8, "mask": 8, "select": 8, "merge_select": 1, "rescore": 1}),
+    (1024, {"gemm": 1, "mask": 1, "select": 1, "merge_select": 0, "rescore": 1})])
+def test_timer_records_one_stage_per_launch_group(cuda_device, chunk, launches):
+    """A Timer on one grouped call, 1000 rows in eight chunks of 128 or in one: every chunk is
+    one record each of the screening GEMM, the exclusion mask and the grouped select (G = 3 fits
+    one launch), the per-chunk lists are merged once (not at all when there is one list), and the
+    G rescores are one record. The timer changes no output bit."""
+    import robot_ebert_amd as ebt
+    from robot_ebert_amd import _lib, search
+    dev = cuda_device
+    n, d, B, k, kp = 1000, 64, 4, 10, 32
+    cat = ebt.Catalog(torch.from_numpy(gaussian(41, n, d, "f32").astype(np.float32)).to(dev))
+    rng = np.random.default_rng(42)
+    masks = ebt.AllowMasks(cat, 3)
+    for i, p in enumerate((0.5, 0.2, 0.05)):
+        masks.from_bool(i, torch.from_numpy(rng.random(n) < p).to(dev))
+    q = torch.from_numpy(gaussian(43, B, d, "f32").astype(np.float32)).to(dev)
+    qb = search.prepare_queries(cat, queries=q)
+    ex = search.csr_from_lists([list(range(b, n, 97)) for b in range(B)], dev)
+    plain = _first_pass(cat, masks, qb, [0, 1, 2], k, kp, chunk, ex, dev)
+    timer = _lib.Timer()
+    timed = _first_pass(cat, masks, qb, [0, 1, 2], k, kp, chunk, ex, dev, timer=timer)
+    torch.cuda.synchronize(dev)
+    got = {}
+    for stage in launches:
+        ms, got[stage] = timer.query(stage)
+        assert np.isfinite(ms) and ms >= 0.0, (stage, ms)
+    assert got == launches
+    for stage in set(_lib.STAGES) - set(launches):
+        assert timer.query(stage)[1] == 0, stage
+    assert torch.equal(timed[0].view(torch.int64), plain[0].view(torch.int64))
+    assert torch.equal(timed[1], plain[1]) and torch.equal(timed[2], plain[2])
+    assert (plain[2] != 99).all() and (plain[1][:, :, 0] >= 0).all()
 
 
 # ---- 4. the fallback itself ---------------------------------------------------------------------
