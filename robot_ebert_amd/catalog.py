@@ -390,3 +390,10 @@ class Catalog:
     def __repr__(self) -> str:
         return (f"Catalog(n={self.n}, d={self.d}, dtype={self.data.dtype}, row_offset="
                 f"{self.row_offset}, image={'native' if self.native else 'f16-normalised'})")
+
+
+def require_whole_catalog(catalog: Catalog, what: str) -> None:
+    """EbertError for a shard of a row-sharded catalog; `what` says what needs one device."""
+    if catalog.n_global != catalog.n:
+        raise EbertError(f"{what}: this catalog is a shard ({catalog.n} of {catalog.n_global} "
+                         "rows)")

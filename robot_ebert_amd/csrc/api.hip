@@ -664,19 +664,30 @@ int ebt_query_dense(const void* q, int dtype, int64_t B, int32_t d, int64_t ldq,
   return query_dense(q, dtype, B, d, ldq, q64, (hipStream_t)stream);
 }
 
+// (the catalog record's image fields stay empty: the sums read the rows and their norms)
+static CatOps liked_cat(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm64) {
+  CatOps c{};
+  c.cat = cat; c.dtype = dtype; c.ld = ld; c.gnorm64 = gnorm64; c.d = d;
+  return c;
+}
+
 int ebt_query_liked_sum(const void* cat, int dtype, int32_t d, int64_t ld,
                         const double* gnorm64_cat, int64_t B, const int64_t* liked_off,
                         const int64_t* liked_rows, double* q64, void* stream) {
-  return query_liked_sum(cat, dtype, d, ld, gnorm64_cat, B, liked_off, liked_rows, q64,
-                         (hipStream_t)stream, 0, 0);
+  return query_liked_sum(liked_cat(cat, dtype, d, ld, gnorm64_cat),
+                         {liked_off, liked_rows, nullptr}, B, q64, (hipStream_t)stream, 0);
 }
 
 int ebt_query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld,
                          const double* gnorm64_cat, int64_t B, const int64_t* liked_off,
                          const int64_t* liked_rows, const double* liked_w, double* q64,
                          void* stream) {
-  return query_liked_wsum(cat, dtype, d, ld, gnorm64_cat, B, liked_off, liked_rows, liked_w, q64,
-                          (hipStream_t)stream, 0, 0);
+  if (!liked_w) {  // (what the shared check cannot see: no weights would select the plain sum)
+    set_error("ebt_query_liked_wsum: bad arguments");
+    return EBT_EINVAL;
+  }
+  return query_liked_sum(liked_cat(cat, dtype, d, ld, gnorm64_cat),
+                         {liked_off, liked_rows, liked_w}, B, q64, (hipStream_t)stream, 0);
 }
 
 int ebt_query_prep(const void* q, int dtype, int64_t B, int64_t B_pad, int32_t d, int64_t ldq,

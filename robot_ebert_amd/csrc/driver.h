@@ -4,6 +4,8 @@
 // function is declared here and defined once, in driver.hip.
 #pragma once
 
+#include <functional>
+
 #include "common.h"
 #include "internal.h"
 
@@ -50,6 +52,21 @@ int prep_dense(const ebt_catalog& c, const void* q, int q_dtype, int64_t B, int6
 int liked_scales(const int64_t* off, const int64_t* rows, int64_t B, int32_t d, int64_t row_lo,
                  int64_t row_hi, std::vector<double>* scale, hipStream_t st,
                  const double* w = nullptr);
+// What a driver says of a liked batch: the rows a list may name, [row_lo, row_hi), and the
+// shard's own row count (n_local, as query_liked_sum's; 0: a whole catalog); whether the caller
+// vouches for the lists (EBT_FLAG_LIKED_CHECKED); the device room for the B float64 scales
+struct LikedBatch {
+  int64_t row_lo, row_hi, n_local;
+  bool checked;
+  double* d_scale; size_t scale_bytes;
+};
+// One liked batch of either driver, in order: liked_scales and the upload of its scales, unless
+// b.checked; the sum of the shard's rows; `reduce` on the sums, if given (the sharded driver's
+// all-reduce); the scale, by the uploaded scales or with b.checked from the CSR on the device;
+// the image
+int prep_liked(const ebt_catalog& c, const LikedCsr& l, int64_t B, const PrepLayout& P, char* base,
+               const LikedBatch& b, hipStream_t st,
+               const std::function<int(double* q64)>& reduce = {});
 
 // ---- the tail of a submit ----------------------------------------------------------------------
 // *ev = an event of the pool, recorded on st (returned to the pool on failure)

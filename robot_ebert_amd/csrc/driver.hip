@@ -247,6 +247,39 @@ int liked_scales(const int64_t* off, const int64_t* rows, int64_t B, int32_t d, 
   return EBT_OK;
 }
 
+// A liked batch, for both drivers (driver.h): checks and scales, the sum, the caller's step, the
+// scale, the image. Validated on the host (counts >= 1 with sklearn's message, rows in
+// [b.row_lo, b.row_hi)) unless the caller did (b.checked): then nothing is read back and the
+// scale comes from the CSR on the device. l.w != NULL: the weighted sum and 1 / W_b in place of
+// the sum and 1 / L_b (l.w == NULL launches what it always did)
+int prep_liked(const ebt_catalog& c, const LikedCsr& l, int64_t B, const PrepLayout& P, char* base,
+               const LikedBatch& b, hipStream_t st,
+               const std::function<int(double* q64)>& reduce) {
+  double* q64 = (double*)(base + P.q64);
+  int rc = EBT_OK;
+  if (!b.checked) {
+    std::vector<double> scale;
+    rc = liked_scales(l.off, l.rows, B, c.d, b.row_lo, b.row_hi, &scale, st, l.w);
+    if (rc) return rc;
+    if (b.scale_bytes < (size_t)B * 8) {
+      set_error("ebt_cosine_topk: workspace too small for the liked-query scales");
+      return EBT_ENOMEM;
+    }
+    rc = hip_check(hipMemcpy(b.d_scale, scale.data(), B * 8, hipMemcpyHostToDevice), "hipMemcpy");
+    if (rc) return rc;
+  }
+  rc = query_liked_sum(cat_ops(c), l, B, q64, st, b.n_local);
+  if (!rc && reduce) rc = reduce(q64);
+  if (rc) return rc;
+  if (b.checked && l.w) rc = scale_by_abs_weight_sum(q64, B, c.d, l.off, l.w, st);
+  else if (b.checked) rc = scale_by_count(q64, B, c.d, l.off, st);
+  else rc = ebt_scale_rows_f64(q64, B, c.d, b.d_scale, st);
+  if (rc) return rc;
+  return ebt_query_image(q64, B, pad_batch(B), c.d, c.img_dtype, nullptr, 0, 0, c.u_cat,
+                         base + P.qimg, c.ld_img, (float*)(base + P.qscale),
+                         (float*)(base + P.eps), st);
+}
+
 // ---- the tail of a submit (driver.h) ------------------------------------------------------------
 int record_event(hipStream_t st, hipEvent_t* ev) {
   *ev = event_get(st);
@@ -342,60 +375,6 @@ __global__ void csr_sorted_kernel(const int64_t* __restrict__ off, const int64_t
   if (bad) flag[0] = 1;
 }
 
-// q64[b] *= 1 / (off[b+1] - off[b]): the 1/L of lib.py:52 from the liked CSR's offsets (the
-// same float64 scale the host computes, then the same product as scale_rows_kernel)
-__global__ void scale_by_count_kernel(double* __restrict__ q64, int64_t total, int d,
-                                      const int64_t* __restrict__ off) {
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
-       t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = t / d;
-    const double s = 1.0 / (double)(off[b + 1] - off[b]);
-    q64[t] *= s;
-  }
-}
-
-// liked path: validated on the host (counts >= 1 with sklearn's message, rows in the catalog),
-// unless the caller did (EBT_FLAG_LIKED_CHECKED): then nothing is read back. w != NULL: the
-// weighted sum and 1 / W_b in place of the sum and 1 / L_b (w == NULL launches what it always did)
-int prep_liked(const ebt_catalog& c, const int64_t* off, const int64_t* rows, const double* w,
-               int64_t B, const PrepLayout& P, char* base, char* scratch, size_t scratch_bytes,
-               hipStream_t st, bool checked) {
-  double* q64 = (double*)(base + P.q64);
-  double* d_scale = (double*)scratch;
-  int rc = EBT_OK;
-  if (!checked) {
-    std::vector<double> scale;
-    rc = liked_scales(off, rows, B, c.d, c.row_offset, c.row_offset + c.n, &scale, st, w);
-    if (rc) return rc;
-    if (scratch_bytes < (size_t)B * 8) {
-      set_error("ebt_cosine_topk: workspace too small for the liked-query scales");
-      return EBT_ENOMEM;
-    }
-    rc = hip_check(hipMemcpy(d_scale, scale.data(), B * 8, hipMemcpyHostToDevice), "hipMemcpy");
-    if (rc) return rc;
-  }
-  rc = w ? query_liked_wsum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, w, q64, st,
-                            c.row_offset, 0)
-         : query_liked_sum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, q64, st,
-                           c.row_offset, 0);
-  if (rc) return rc;
-  if (checked && w) {
-    rc = scale_by_abs_weight_sum(q64, B, c.d, off, w, st);
-  } else if (checked) {
-    int64_t blocks = ceil_div(B * c.d, 256);
-    blocks = blocks > 8192 ? 8192 : blocks;
-    hipLaunchKernelGGL(scale_by_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, q64,
-                       B * c.d, c.d, off);
-    rc = launch_check("scale_by_count_kernel");
-  } else {
-    rc = ebt_scale_rows_f64(q64, B, c.d, d_scale, st);
-  }
-  if (rc) return rc;
-  return ebt_query_image(q64, B, pad_batch(B), c.d, c.img_dtype, nullptr, 0, 0, c.u_cat,
-                         base + P.qimg, c.ld_img, (float*)(base + P.qscale),
-                         (float*)(base + P.eps), st);
-}
-
 int run_prepared(const ebt_catalog& c, const PrepLayout& P, char* base, int64_t B,
                  const int64_t* excl_off, const int64_t* excl_rows, int32_t k_eff, int32_t kp,
                  int64_t chunk, int flags, char* pass, size_t pass_bytes, double* out_s,
@@ -481,11 +460,12 @@ int ebt_cosine_topk_weighted_submit(const ebt_catalog* cat, const void* q, int q
   }
   char* ws = (char*)workspace;
   char* prep = ws + L.off_prep;
+  const LikedBatch liked_batch{cat->row_offset, cat->row_offset + cat->n, 0,
+                               (o.flags & EBT_FLAG_LIKED_CHECKED) != 0,
+                               (double*)(ws + (L.large ? L.off_big : L.off_pass)),
+                               L.large ? L.big_bytes : L.pass_bytes};
   int rc = q ? prep_dense(*cat, q, q_dtype, B, ldq, L.prep, prep, st)
-             : prep_liked(*cat, liked_off, liked_rows, liked_w, B, L.prep, prep,
-                          ws + (L.large ? L.off_big : L.off_pass),
-                          L.large ? L.big_bytes : L.pass_bytes, st,
-                          (o.flags & EBT_FLAG_LIKED_CHECKED) != 0);
+             : prep_liked(*cat, {liked_off, liked_rows, liked_w}, B, L.prep, prep, liked_batch, st);
   if (rc) return rc;
   int32_t* cert = (int32_t*)(ws + L.off_cert);
   // the full-sort path fills its certificates by a memset and adds the exclusion flag: copied

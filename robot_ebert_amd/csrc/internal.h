@@ -12,11 +12,11 @@
 //     and linkage, so that kernel symbols do not change; its name is unique in the library.
 //   * A type shared by two files is defined in exactly one header (common.h, here, driver.h) under
 //     a name that no .hip file defines. Here: the operand records QueryOps, CatOps, ExclCsr,
-//     HitSlots, LeadIn, GatheredSamples, PipeArgs, WaveMergeOpts, CandList, RescoreExtras and
-//     the unfused path's ChunkPlan -- host-only aggregates, filled by name at the one place where
-//     positional arguments come in -- and StageScope, the timed stage of every file: its
-//     constructor and destructor are api.hip's, where the timer behind its handle (Timer) stays
-//     file-local, as do KernelStage and WsLayout.
+//     LikedCsr, HitSlots, LeadIn, GatheredSamples, PipeArgs, WaveMergeOpts, CandList,
+//     RescoreExtras and the unfused path's ChunkPlan -- host-only aggregates, filled by name at
+//     the one place where positional arguments come in -- and StageScope, the timed stage of
+//     every file: its constructor and destructor are api.hip's, where the timer behind its
+//     handle (Timer) stays file-local, as do KernelStage and WsLayout.
 //   * A function with external linkage is declared in common.h, here, or in driver.h.
 #pragma once
 
@@ -44,6 +44,8 @@ inline CatOps cat_ops(const ebt_catalog& c) {
 }
 // Per-query excluded rows as a CSR (both null: none)
 struct ExclCsr { const int64_t *off, *rows; };
+// Per-query liked rows as a CSR, w parallel to rows (null: the unweighted sum)
+struct LikedCsr { const int64_t *off, *rows; const double* w; };
 // The filter GEMM's per-group hit slots: group g of query b holds counts[b * ld_counts + g] hits
 // at cand[b * ld_cand + g * slots ...]; from_group: the same slots seen from group g on
 struct HitSlots {
@@ -202,13 +204,15 @@ int screen_image(const void* x, int dtype, int64_t n, int32_t d, int64_t ld, con
                  unsigned int* err_max = nullptr);
 int query_dense(const void* q, int dtype, int64_t B, int32_t d, int64_t ldq, double* q64,
                 hipStream_t st);
-int query_liked_sum(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm,
-                    int64_t B, const int64_t* off, const int64_t* rows, double* q64,
-                    hipStream_t st, int64_t row_offset, int64_t n_local);
-// the weighted sum sum_l w_l x_l / g_l (wts parallel to rows), and q64[b] *= 1 / sum_l |w_l|
-int query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm,
-                     int64_t B, const int64_t* off, const int64_t* rows, const double* wts,
-                     double* q64, hipStream_t st, int64_t row_offset, int64_t n_local);
+// q64[b] = sum_l x_l / g_l over l's rows that lie in the shard (n_local > 0: rows outside
+// [c.row_offset, c.row_offset + n_local) are skipped), or with l.w sum_l w_l x_l / g_l. Of c:
+// cat, dtype, ld, gnorm64, d, row_offset. It checks these operands itself (null pointers, d,
+// ld, dtype 0..3; with l.w also l.rows) and reports them as "ebt_query_liked_sum: bad arguments",
+// or "ebt_query_liked_wsum: ..." with l.w: the drivers' valid_catalog does not test dtype
+int query_liked_sum(const CatOps& c, const LikedCsr& l, int64_t B, double* q64, hipStream_t st,
+                    int64_t n_local);
+// q64[b] *= 1 / L_b from the CSR's offsets, and q64[b] *= 1 / sum_l |w_l|
+int scale_by_count(double* q64, int64_t B, int32_t d, const int64_t* off, hipStream_t st);
 int scale_by_abs_weight_sum(double* q64, int64_t B, int32_t d, const int64_t* off,
                             const double* wts, hipStream_t st);
 int scale_rows_f64(double* q64, int64_t B, int32_t d, const double* scale, hipStream_t st);

@@ -7,11 +7,12 @@
 //                      (constants.py:55-56) and is kept resident in HBM.
 //  * screen_image   -- the f16/bf16 MFMA operand of a matrix (normalised or raw), zero-padded to
 //                      a multiple of 64 columns.
-//  * query_dense / query_liked_sum / scale_rows -- q64 = normalize(q), or the liked-row mean of
-//                      lib.py:51-52 folded into ONE query vector per user (sum here, 1/L later).
-//  * query_liked_wsum / scale_by_abs_weight_sum -- the same fold with a float64 weight per liked
-//                      row (ABI 0.8.0: lib.py:47-52's 0/1 vote generalised): sum_l w_l x_l/|x_l|,
-//                      then 1 / sum_l |w_l|.
+//  * query_dense / query_liked_sum / scale_rows / scale_by_count -- q64 = normalize(q), or the
+//                      liked-row mean of lib.py:51-52 folded into ONE query vector per user (sum
+//                      here, 1/L later: from uploaded scales, or from the CSR's offsets).
+//  * query_liked_sum with weights / scale_by_abs_weight_sum -- the same fold with a float64
+//                      weight per liked row (ABI 0.8.0: lib.py:47-52's 0/1 vote generalised):
+//                      sum_l w_l x_l/|x_l|, then 1 / sum_l |w_l|.
 //  * query_image    -- the query's MFMA operand, its epilogue scale and the certification bound.
 //  * mask_excluded  -- rated movies are not candidates (lib.py:48,55).
 #include "common.h"
@@ -264,141 +265,20 @@ int query_dense(const void* q, int dtype, int64_t B, int32_t d, int64_t ldq, dou
   return launch_check("query_dense_kernel");
 }
 
-// n_local > 0: rows outside [row_offset, row_offset + n_local) are skipped (a row-sharded
-// catalog: each shard sums its own liked rows; the caller adds the shards' partial sums)
-template <int DT>
-__global__ __launch_bounds__(256) void query_liked_kernel(const void* __restrict__ cat, int d,
-                                                           int64_t ld,
-                                                           const double* __restrict__ gnorm,
-                                                           const int64_t* __restrict__ off,
-                                                           const int64_t* __restrict__ rows,
-                                                           int64_t row_offset, int64_t n_local,
-                                                           double* __restrict__ q64) {
-  const int64_t b = blockIdx.x;
-  const int64_t l0 = off[b], l1 = off[b + 1];
-  for (int j = threadIdx.x; j < d; j += blockDim.x) {
-    double acc = 0.0;
-    for (int64_t l = l0; l < l1; ++l) {
-      const int64_t r = rows[l] - row_offset;
-      if (n_local > 0 && (r < 0 || r >= n_local)) continue;
-      acc += load_as_f64<DT>(cat, r * ld + j) / gnorm[r];
-    }
-    q64[b * d + j] = acc;
-  }
-}
-
-// The same sums for 16-byte-aligned rows (ld * size and the base 16-byte aligned, d a multiple of
-// the elements per 16 bytes): the query's rows and norms staged in LDS, each thread owning whole
-// 16-byte chunks of the row, UL liked rows' chunks loaded before any is added (the loop above
-// waits for every element load in turn). The per-element sum runs over the liked rows in the
-// same order with the same operations: bit-identical to query_liked_kernel.
-constexpr int QL_STAGE = 256;   // liked rows staged per round
-constexpr int QL_UL = 8;        // liked rows in flight per chunk
-template <int DT>
-__global__ __launch_bounds__(256) void query_liked_vec_kernel(
-    const void* __restrict__ cat, int d, int64_t ld, const double* __restrict__ gnorm,
-    const int64_t* __restrict__ off, const int64_t* __restrict__ rows, int64_t row_offset,
-    int64_t n_local, double* __restrict__ q64) {
-  constexpr int ES = DT == EBT_F64 ? 8 : (DT == EBT_F32 ? 4 : 2);
-  constexpr int PER = 16 / ES;   // elements per 16-byte chunk
-  __shared__ int64_t srow[QL_STAGE];
-  __shared__ double sg[QL_STAGE];
-  const int64_t b = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int64_t l0 = off[b], l1 = off[b + 1];
-  const int nch = d / PER;
-  // a thread's chunks: c = tid, tid + 256, ... (at most QL_CPT of them: d <= 256 * PER * QL_CPT)
-  constexpr int QL_CPT = 2;
-  double acc[QL_CPT][PER];
-#pragma unroll
-  for (int i = 0; i < QL_CPT; ++i)
-#pragma unroll
-    for (int e = 0; e < PER; ++e) acc[i][e] = 0.0;
-  for (int64_t s0 = l0; s0 < l1; s0 += QL_STAGE) {
-    const int ns = l1 - s0 < QL_STAGE ? (int)(l1 - s0) : QL_STAGE;
-    __syncthreads();
-    if (tid < ns) {
-      const int64_t r = rows[s0 + tid] - row_offset;
-      const bool skip = n_local > 0 && (r < 0 || r >= n_local);   // another shard's row
-      srow[tid] = skip ? -1 : r;
-      sg[tid] = skip ? 1.0 : gnorm[r];
-    }
-    __syncthreads();
-    for (int u0 = 0; u0 < ns; u0 += QL_UL) {
-#pragma unroll
-      for (int i = 0; i < QL_CPT; ++i) {
-        const int c = tid + 256 * i;
-        if (c >= nch) break;
-        uint4 raw[QL_UL];
-#pragma unroll
-        for (int u = 0; u < QL_UL; ++u) {   // loads first (a skipped / past-the-end row reads row 0)
-          const int64_t r = u0 + u < ns ? srow[u0 + u] : -1;
-          raw[u] = *(const uint4*)((const char*)cat + ((r >= 0 ? r : 0) * ld + (int64_t)c * PER) * ES);
-        }
-#pragma unroll
-        for (int u = 0; u < QL_UL; ++u) {
-          if (u0 + u >= ns || srow[u0 + u] < 0) continue;
-          const double g = sg[u0 + u];
-#pragma unroll
-          for (int e = 0; e < PER; ++e) {
-            double x;
-            if constexpr (DT == EBT_F32) x = (double)((const float*)&raw[u])[e];
-            else if constexpr (DT == EBT_F64) x = ((const double*)&raw[u])[e];
-            else if constexpr (DT == EBT_BF16) x = bf16_bits_to_f64(((const uint16_t*)&raw[u])[e]);
-            else x = f16_bits_to_f64(((const uint16_t*)&raw[u])[e]);
-            acc[i][e] += x / g;
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < QL_CPT; ++i) {
-    const int c = tid + 256 * i;
-    if (c >= nch) break;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) q64[b * d + (int64_t)c * PER + e] = acc[i][e];
-  }
-}
-
-// rows are catalog rows + row_offset (the self-contained path passes GLOBAL rows; the caller
-// guarantees every row lies inside the catalog)
-int query_liked_sum(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm,
-                    int64_t B, const int64_t* off, const int64_t* rows, double* q64,
-                    hipStream_t st, int64_t row_offset, int64_t n_local) {
-  if (!cat || !gnorm || !off || !q64 || B < 0 || d <= 0 || ld < d || dtype < 0 || dtype > 3) {
-    set_error("ebt_query_liked_sum: bad arguments");
-    return EBT_EINVAL;
-  }
-  if (B == 0) return EBT_OK;
-  dim3 grid((unsigned)B), block(256);
-  // the chunk form: whole 16-byte chunks, at most two per thread
-  const bool vec = vec_ok(cat, dtype, ld, d) && d <= 256 * (16 / dtype_size(dtype)) * 2;
-  for_dtype(dtype, [&](auto dt) {
-    constexpr int DT = decltype(dt)::value;
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, block, 0, st, cat, d, ld, gnorm, off, rows, row_offset,
-                         n_local, q64);
-    };
-    if (vec) launch(query_liked_vec_kernel<DT>);
-    else launch(query_liked_kernel<DT>);
-  });
-  return launch_check(vec ? "query_liked_vec_kernel" : "query_liked_kernel");
-}
-
-// ------------------------------------------------------- weighted liked rows (ABI 0.8.0) ----
-// q64[b] = sum_l w_l (x_{r_l} / gnorm[r_l]) in CSR order: the two kernels above with one multiply
-// per row (their instantiations are not touched). The term is the ROUNDED product w * (x / g),
-// then added: no fused multiply-add, so that the element form, the chunk form and a float64 host
-// loop give the same bits (and a weight of 1.0 gives the unweighted kernels' bits).
+// q64[b] = sum_l x_{r_l} / gnorm[r_l] in CSR order, or with W sum_l w_l (x_{r_l} / gnorm[r_l])
+// (wts parallel to rows, ABI 0.8.0). The weighted term is the ROUNDED product w * (x / g), then
+// added: no fused multiply-add, so that the element form, the chunk form and a float64 host loop
+// give the same bits (and a weight of 1.0 gives the unweighted sum's bits).
 __device__ __forceinline__ double weighted_term(double w, double xg) {
 #pragma clang fp contract(off)
   const double t = w * xg;
   return t;
 }
 
-template <int DT>
-__global__ __launch_bounds__(256) void query_liked_w_kernel(
+// n_local > 0: rows outside [row_offset, row_offset + n_local) are skipped (a row-sharded
+// catalog: each shard sums its own liked rows; the caller adds the shards' partial sums)
+template <int DT, bool W>
+__global__ __launch_bounds__(256) void query_liked_kernel(
     const void* __restrict__ cat, int d, int64_t ld, const double* __restrict__ gnorm,
     const int64_t* __restrict__ off, const int64_t* __restrict__ rows,
     const double* __restrict__ wts, int64_t row_offset, int64_t n_local,
@@ -410,15 +290,24 @@ __global__ __launch_bounds__(256) void query_liked_w_kernel(
     for (int64_t l = l0; l < l1; ++l) {
       const int64_t r = rows[l] - row_offset;
       if (n_local > 0 && (r < 0 || r >= n_local)) continue;
-      acc += weighted_term(wts[l], load_as_f64<DT>(cat, r * ld + j) / gnorm[r]);
+      const double xg = load_as_f64<DT>(cat, r * ld + j) / gnorm[r];
+      if constexpr (W) acc += weighted_term(wts[l], xg);
+      else acc += xg;
     }
     q64[b * d + j] = acc;
   }
 }
 
-// the chunk form: the weights staged in LDS beside the rows and norms
-template <int DT>
-__global__ __launch_bounds__(256) void query_liked_w_vec_kernel(
+// The same sums for 16-byte-aligned rows (ld * size and the base 16-byte aligned, d a multiple of
+// the elements per 16 bytes): the query's rows and norms (and weights) staged in LDS, each thread
+// owning whole 16-byte chunks of the row, UL liked rows' chunks loaded before any is added (the
+// loop above waits for every element load in turn). The per-element sum runs over the liked rows
+// in the same order with the same operations: bit-identical to query_liked_kernel.
+constexpr int QL_STAGE = 256;   // liked rows staged per round
+constexpr int QL_UL = 8;        // liked rows in flight per chunk
+constexpr int QL_CPT = 2;       // chunks per thread: d <= 256 * (elements per chunk) * QL_CPT
+template <int DT, bool W>
+__global__ __launch_bounds__(256) void query_liked_vec_kernel(
     const void* __restrict__ cat, int d, int64_t ld, const double* __restrict__ gnorm,
     const int64_t* __restrict__ off, const int64_t* __restrict__ rows,
     const double* __restrict__ wts, int64_t row_offset, int64_t n_local,
@@ -427,12 +316,12 @@ __global__ __launch_bounds__(256) void query_liked_w_vec_kernel(
   constexpr int PER = 16 / ES;   // elements per 16-byte chunk
   __shared__ int64_t srow[QL_STAGE];
   __shared__ double sg[QL_STAGE];
-  __shared__ double sw[QL_STAGE];
+  __shared__ double sw[W ? QL_STAGE : 1];   // (unweighted: never referenced, takes no LDS)
   const int64_t b = blockIdx.x;
   const int tid = threadIdx.x;
   const int64_t l0 = off[b], l1 = off[b + 1];
   const int nch = d / PER;
-  constexpr int QL_CPT = 2;   // chunks per thread (d <= 256 * PER * QL_CPT)
+  // a thread's chunks: c = tid, tid + 256, ... (at most QL_CPT of them)
   double acc[QL_CPT][PER];
 #pragma unroll
   for (int i = 0; i < QL_CPT; ++i)
@@ -446,7 +335,7 @@ __global__ __launch_bounds__(256) void query_liked_w_vec_kernel(
       const bool skip = n_local > 0 && (r < 0 || r >= n_local);   // another shard's row
       srow[tid] = skip ? -1 : r;
       sg[tid] = skip ? 1.0 : gnorm[r];
-      sw[tid] = wts[s0 + tid];
+      if constexpr (W) sw[tid] = wts[s0 + tid];
     }
     __syncthreads();
     for (int u0 = 0; u0 < ns; u0 += QL_UL) {
@@ -464,7 +353,8 @@ __global__ __launch_bounds__(256) void query_liked_w_vec_kernel(
         for (int u = 0; u < QL_UL; ++u) {
           if (u0 + u >= ns || srow[u0 + u] < 0) continue;
           const double g = sg[u0 + u];
-          const double w = sw[u0 + u];
+          [[maybe_unused]] double w;
+          if constexpr (W) w = sw[u0 + u];
 #pragma unroll
           for (int e = 0; e < PER; ++e) {
             double x;
@@ -472,7 +362,8 @@ __global__ __launch_bounds__(256) void query_liked_w_vec_kernel(
             else if constexpr (DT == EBT_F64) x = ((const double*)&raw[u])[e];
             else if constexpr (DT == EBT_BF16) x = bf16_bits_to_f64(((const uint16_t*)&raw[u])[e]);
             else x = f16_bits_to_f64(((const uint16_t*)&raw[u])[e]);
-            acc[i][e] += weighted_term(w, x / g);
+            if constexpr (W) acc[i][e] += weighted_term(w, x / g);
+            else acc[i][e] += x / g;
           }
         }
       }
@@ -487,32 +378,40 @@ __global__ __launch_bounds__(256) void query_liked_w_vec_kernel(
   }
 }
 
-int query_liked_wsum(const void* cat, int dtype, int32_t d, int64_t ld, const double* gnorm,
-                     int64_t B, const int64_t* off, const int64_t* rows, const double* wts,
-                     double* q64, hipStream_t st, int64_t row_offset, int64_t n_local) {
-  if (!cat || !gnorm || !off || !rows || !wts || !q64 || B < 0 || d <= 0 || ld < d || dtype < 0 ||
-      dtype > 3) {
-    set_error("ebt_query_liked_wsum: bad arguments");
+// l.rows are catalog rows + c.row_offset (the self-contained path passes GLOBAL rows; the caller
+// guarantees every row lies inside the catalog); l.w == null: the unweighted sum. The operands
+// are checked here for the C entries and the drivers alike (an ebt_catalog is caller-filled and
+// its dtype is tested nowhere else on the liked path), under the name of the entry that l.w selects
+int query_liked_sum(const CatOps& c, const LikedCsr& l, int64_t B, double* q64, hipStream_t st,
+                    int64_t n_local) {
+  if (!c.cat || !c.gnorm64 || !l.off || (l.w && !l.rows) || !q64 || B < 0 || c.d <= 0 ||
+      c.ld < c.d || c.dtype < 0 || c.dtype > 3) {
+    set_error("%s: bad arguments", l.w ? "ebt_query_liked_wsum" : "ebt_query_liked_sum");
     return EBT_EINVAL;
   }
   if (B == 0) return EBT_OK;
   dim3 grid((unsigned)B), block(256);
-  const bool vec = vec_ok(cat, dtype, ld, d) && d <= 256 * (16 / dtype_size(dtype)) * 2;
-  for_dtype(dtype, [&](auto dt) {
-    constexpr int DT = decltype(dt)::value;
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, block, 0, st, cat, d, ld, gnorm, off, rows, wts, row_offset,
-                         n_local, q64);
-    };
-    if (vec) launch(query_liked_w_vec_kernel<DT>);
-    else launch(query_liked_w_kernel<DT>);
+  // the chunk form: whole 16-byte chunks, at most QL_CPT per thread
+  const bool vec = vec_ok(c.cat, c.dtype, c.ld, c.d) &&
+                   c.d <= 256 * (16 / dtype_size(c.dtype)) * QL_CPT;
+  for_dtype(c.dtype, [&](auto dt) {
+    for_bool(l.w != nullptr, [&](auto wt) {
+      constexpr int DT = decltype(dt)::value;
+      constexpr bool W = decltype(wt)::value;
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, block, 0, st, c.cat, c.d, c.ld, c.gnorm64, l.off, l.rows,
+                           l.w, c.row_offset, n_local, q64);
+      };
+      if (vec) launch(query_liked_vec_kernel<DT, W>);
+      else launch(query_liked_kernel<DT, W>);
+    });
   });
-  return launch_check(vec ? "query_liked_w_vec_kernel" : "query_liked_w_kernel");
+  return launch_check(vec ? "query_liked_vec_kernel" : "query_liked_kernel");
 }
 
 // q64[b] *= 1 / W_b, W_b = the sequential float64 sum of |w_l| over the query's CSR segment (the
-// value the host check computes, then scale_rows_kernel's product): the weighted twin of the
-// driver's scale by 1 / L for a CSR the caller has checked. One block per query; thread 0 sums.
+// value the host check computes, then scale_rows_kernel's product): the weighted twin of
+// scale_by_count for a CSR the caller has checked. One block per query; thread 0 sums.
 __global__ __launch_bounds__(256) void scale_by_abs_weight_sum_kernel(
     double* __restrict__ q64, int d, const int64_t* __restrict__ off,
     const double* __restrict__ wts) {
@@ -557,6 +456,26 @@ int scale_rows_f64(double* q64, int64_t B, int32_t d, const double* scale, hipSt
   hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, q64, B * d, d,
                      scale);
   return launch_check("scale_rows_kernel");
+}
+
+// q64[b] *= 1 / (off[b+1] - off[b]): the 1/L of lib.py:52 from the liked CSR's offsets (the
+// same float64 scale the host computes, then the same product as scale_rows_kernel)
+__global__ void scale_by_count_kernel(double* __restrict__ q64, int64_t total, int d,
+                                      const int64_t* __restrict__ off) {
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = t / d;
+    const double s = 1.0 / (double)(off[b + 1] - off[b]);
+    q64[t] *= s;
+  }
+}
+
+int scale_by_count(double* q64, int64_t B, int32_t d, const int64_t* off, hipStream_t st) {
+  int64_t blocks = ceil_div(B * d, 256);
+  blocks = blocks > 8192 ? 8192 : blocks;
+  hipLaunchKernelGGL(scale_by_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, q64, B * d,
+                     d, off);
+  return launch_check("scale_by_count_kernel");
 }
 
 // ---------------------------------------------------------------------- query image/eps ----

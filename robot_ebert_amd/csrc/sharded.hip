@@ -181,23 +181,12 @@ int sh_gather(const ebt_comm& cm, const void* send, void* recv, size_t bytes, vo
 }
 
 // liked rows of a row-sharded catalog: GLOBAL rows, each shard sums its own, the partial sums
-// are all-gathered and added in rank order, then / L_b (lib.py:51-52). With weights w (the
-// same global list on every rank): each shard's weighted sum of its own rows, then / W_b, which
-// every rank computes from the full list
-int prep_liked_sharded(const ebt_catalog& c, const ebt_comm& cm, const int64_t* off,
-                       const int64_t* rows, const double* w, int64_t B, const PrepLayout& P,
-                       char* base, double* d_scale, double* qrecv, void* timer, hipStream_t st) {
-  std::vector<double> scale;
-  int rc = liked_scales(off, rows, B, c.d, 0, cm.n_global, &scale, st, w);
-  if (rc) return rc;
-  rc = hip_check(hipMemcpy(d_scale, scale.data(), B * 8, hipMemcpyHostToDevice), "hipMemcpy");
-  if (rc) return rc;
-  double* q64 = (double*)(base + P.q64);
-  rc = w ? query_liked_wsum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, w, q64, st,
-                            c.row_offset, c.n)
-         : query_liked_sum(c.data, c.dtype, c.d, c.ld, c.gnorm64, B, off, rows, q64, st,
-                           c.row_offset, c.n);
-  if (rc) return rc;
+// are all-gathered and added in rank order (or all-reduced by the caller), then / L_b
+// (lib.py:51-52). With weights (the same global list on every rank): each shard's weighted sum
+// of its own rows, then / W_b, which every rank computes from the full list. This is
+// prep_liked's step between the sum and the scale
+int reduce_liked_sums(const ebt_catalog& c, const ebt_comm& cm, int64_t B, double* q64,
+                      double* qrecv, void* timer, hipStream_t st) {
   if (cm.all_reduce_f64) {  // the caller's all-reduce (RCCL: about 2 / R of the gather's bytes)
     int e;
     {
@@ -208,18 +197,13 @@ int prep_liked_sharded(const ebt_catalog& c, const ebt_comm& cm, const int64_t* 
       set_error("ebt_cosine_topk_sharded: the caller's all_reduce_f64 returned %d", e);
       return EBT_EHIP;
     }
-  } else {
-    rc = sh_gather(cm, q64, qrecv, (size_t)B * c.d * 8, timer, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(sum_ranks_kernel, dim3(grid_for(B * c.d)), dim3(256), 0, st, qrecv,
-                       (int)cm.world, B * c.d, q64);
-    rc = launch_check("sum_ranks_kernel");
+    return EBT_OK;
   }
-  if (!rc) rc = ebt_scale_rows_f64(q64, B, c.d, d_scale, st);
+  const int rc = sh_gather(cm, q64, qrecv, (size_t)B * c.d * 8, timer, st);
   if (rc) return rc;
-  return ebt_query_image(q64, B, pad_batch(B), c.d, c.img_dtype, nullptr, 0, 0, c.u_cat,
-                         base + P.qimg, c.ld_img, (float*)(base + P.qscale),
-                         (float*)(base + P.eps), st);
+  hipLaunchKernelGGL(sum_ranks_kernel, dim3(grid_for(B * c.d)), dim3(256), 0, st, qrecv,
+                     (int)cm.world, B * c.d, q64);
+  return launch_check("sum_ranks_kernel");
 }
 
 // the full exchange: every shard's [B][k] exact list (f64 scores, i64 rows), ebt_merge_topk
@@ -296,13 +280,18 @@ int ebt_cosine_topk_sharded_weighted_submit(
   const float* qscale = (const float*)(prep + L.prep.qscale);
   const float* qeps = (const float*)(prep + L.prep.eps);
   int rc = EBT_OK;
-  // 1. the queries (lib.py:51-52)
+  // 1. the queries (lib.py:51-52): liked rows are GLOBAL, each shard sums its own, the lists are
+  // always checked here, and the scales have a region of their own (B float64)
+  const LikedBatch liked_batch{0, cm.n_global, c.n, false, (double*)(ws + S.off_scale),
+                               (size_t)B * 8};
   {
     StageScope s(timer, EBT_STAGE_PREP, st);
     rc = q ? prep_dense(c, q, q_dtype, B, ldq, L.prep, prep, st)
-           : prep_liked_sharded(c, cm, liked_off, liked_rows, liked_w, B, L.prep, prep,
-                                (double*)(ws + S.off_scale), (double*)(ws + S.off_qrecv), timer,
-                                st);
+           : prep_liked(c, {liked_off, liked_rows, liked_w}, B, L.prep, prep, liked_batch, st,
+                        [&](double* sums) {
+                          return reduce_liked_sums(c, cm, B, sums, (double*)(ws + S.off_qrecv),
+                                                   timer, st);
+                        });
   }
   if (rc) return rc;
   // 2. the catalog-wide screening threshold from every shard's sample maxima (taken by the

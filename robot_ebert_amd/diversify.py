@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import EbertError, call, ptr, require_cuda, stream_of
-from .catalog import Catalog
+from .catalog import Catalog, require_whole_catalog
 
 
 class Diversified(NamedTuple):
@@ -32,12 +32,6 @@ class Diversified(NamedTuple):
     scores: torch.Tensor   # float64 [B, k]: their relevances (the input's bits), NaN padded
     mmr: torch.Tensor      # float64 [B, k]: the value each pick maximised, NaN padded
     pos: torch.Tensor      # int32 [B, k]: their positions in the pool, -1 padded
-
-
-def _check_catalog(catalog: Catalog) -> None:
-    if catalog.n_global != catalog.n:
-        raise EbertError("diversification needs the pool rows on one device: this catalog is a "
-                         f"shard ({catalog.n} of {catalog.n_global} rows)")
 
 
 def _check_lam(lam) -> float:
@@ -78,7 +72,7 @@ def pool_gram(catalog: Catalog, rows: torch.Tensor) -> Tuple[torch.Tensor, torch
     """``ebt_pool_gram``: (gram float64 [B, p, p], status int32 [B]); ``gram[b, i, j]`` is the
     cosine between pool slots i and j of query b, NaN where either is empty (-1). The status is
     left on the device (1, or -2 for a query with a row outside the catalog: all NaN)."""
-    _check_catalog(catalog)
+    require_whole_catalog(catalog, "diversification needs the pool rows on one device")
     B, p = _shape_of(rows, "rows")
     _check_pool(p)
     rows = _pool_rows(rows)
@@ -134,7 +128,7 @@ def diversify_topk(catalog: Catalog, scores: torch.Tensor, rows: torch.Tensor, k
 
     A pool row outside the catalog is never read and raises EbertError naming the query; a
     row-sharded catalog raises EbertError."""
-    _check_catalog(catalog)
+    require_whole_catalog(catalog, "diversification needs the pool rows on one device")
     lam = _check_lam(lam)
     B, p = _shape_of(rows, "rows")
     _check_pool(p)

@@ -25,8 +25,11 @@ import torch
 
 from . import _lib
 from ._lib import EbertError, call, ptr, require_cuda, stream_of
-from .catalog import Catalog
-from .search import check_weights
+from .catalog import Catalog, require_whole_catalog
+from .search import check_weights, device_liked_weights, parse_weight_lists
+
+
+_ONE_DEVICE = "explanations need the liked rows and the result rows on one device"
 
 
 class Explanation(NamedTuple):
@@ -52,16 +55,7 @@ def _liked_csr(liked, liked_weights, dev) -> Tuple[torch.Tensor, torch.Tensor,
         off_h = off.cpu().numpy()
         w = None
         if liked_weights is not None:
-            if not isinstance(liked_weights, torch.Tensor):
-                raise EbertError("with a device CSR, liked_weights must be a device float64 "
-                                 "[nnz] tensor")
-            require_cuda(liked_weights, "liked_weights")
-            if liked_weights.dtype != torch.float64 or liked_weights.dim() != 1 \
-                    or liked_weights.numel() != rows.numel():
-                raise EbertError(f"liked_weights must be float64 [{int(rows.numel())}] (one per "
-                                 f"liked row), got {liked_weights.dtype} "
-                                 f"{tuple(liked_weights.shape)}")
-            w = liked_weights.contiguous()
+            w = device_liked_weights(liked_weights, int(rows.numel()))
             check_weights(off_h, w.cpu().numpy())
         return off, rows, w, off_h
     if isinstance(liked_weights, torch.Tensor):
@@ -73,27 +67,11 @@ def _liked_csr(liked, liked_weights, dev) -> Tuple[torch.Tensor, torch.Tensor,
     flat = np.concatenate(segs) if segs and off_h[-1] else np.zeros(1, dtype=np.int64)
     w = None
     if liked_weights is not None:
-        if len(liked_weights) != len(segs):
-            raise EbertError(f"{len(liked_weights)} weight lists for {len(segs)} liked lists")
-        ws = []
-        for b, (s, x) in enumerate(zip(segs, liked_weights)):
-            try:
-                x = np.asarray(x, dtype=np.float64).ravel()
-            except (TypeError, ValueError) as e:
-                raise EbertError(f"liked weights of query {b}: {e}") from None
-            if x.size != s.size:
-                raise EbertError(f"query {b} has {x.size} weights for {s.size} liked rows")
-            ws.append(x)
+        _, ws = parse_weight_lists(segs, liked_weights)
         wflat = np.concatenate(ws) if ws and off_h[-1] else np.zeros(1)
         check_weights(off_h, wflat)
         w = torch.from_numpy(wflat).to(dev)
     return torch.from_numpy(off_h).to(dev), torch.from_numpy(flat).to(dev), w, off_h
-
-
-def _check_catalog(catalog: Catalog) -> None:
-    if catalog.n_global != catalog.n:
-        raise EbertError("explanations need the liked rows and the result rows on one device: "
-                         f"this catalog is a shard ({catalog.n} of {catalog.n_global} rows)")
 
 
 def _result_rows(catalog: Catalog, rows: torch.Tensor, B: int) -> torch.Tensor:
@@ -110,7 +88,7 @@ def liked_contrib(catalog: Catalog, rows: torch.Tensor, liked,
     """``ebt_liked_contrib``: the whole contribution matrix, CSR-shaped. Returns (out float64
     [k * nnz], status int32 [B], liked offsets, liked rows); query b's block is
     ``out[k * off[b] : k * off[b + 1]].view(k, L_b)``. The status is left on the device."""
-    _check_catalog(catalog)
+    require_whole_catalog(catalog, _ONE_DEVICE)
     dev = catalog.device
     off, lrows, w, off_h = _liked_csr(liked, liked_weights, dev)
     B = int(off.numel()) - 1
@@ -155,7 +133,7 @@ def explain_topk(catalog: Catalog, rows: torch.Tensor,
     catalog is never read and raises EbertError naming the query; a query without a liked row
     raises sklearn's ValueError, as ``score_topk`` does. A row-sharded catalog raises EbertError.
     """
-    _check_catalog(catalog)
+    require_whole_catalog(catalog, _ONE_DEVICE)
     if not 1 <= int(m) <= _lib.EBT_EXPLAIN_M_MAX:
         raise EbertError(f"m={m} is outside [1, {_lib.EBT_EXPLAIN_M_MAX}]")
     dev = catalog.device

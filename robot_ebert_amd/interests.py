@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import EbertError, call, ptr, stream_of
-from .catalog import Catalog
+from .catalog import Catalog, require_whole_catalog
 from .search import score_topk
 
 _SKLEARN_EMPTY = ("Found array with 0 sample(s) (shape=(0, {d})) while a minimum of 1 is required "
@@ -49,12 +49,6 @@ class MultiInterest(NamedTuple):
     pos: torch.Tensor         # int32 [B, k]: its rank in that cluster's own top k, -1 padded
     size: torch.Tensor        # int32 [B, c]: members per cluster (cluster_liked's)
     medoid_row: torch.Tensor  # int64 [B, c]: the GLOBAL row of each cluster's medoid, -1 = none
-
-
-def _check_catalog(catalog: Catalog) -> None:
-    if catalog.n_global != catalog.n:
-        raise EbertError("multi-interest search needs the liked rows on one device: this catalog "
-                         f"is a shard ({catalog.n} of {catalog.n_global} rows)")
 
 
 def _check_c(c) -> int:
@@ -97,7 +91,7 @@ def cluster_liked(catalog: Catalog, liked, c: int = 3, ws_budget: int = 1 << 30)
     A list longer than 512 rows or with a row outside the catalog raises EbertError naming the
     query (no such row is read); a row-sharded catalog raises EbertError; an empty list raises
     sklearn's ValueError, as ``score_topk`` does."""
-    _check_catalog(catalog)
+    require_whole_catalog(catalog, "multi-interest search needs the liked rows on one device")
     c = _check_c(c)
     lists = _host_lists(liked, "liked")
     B = len(lists)
@@ -227,7 +221,7 @@ def multi_interest_topk(catalog: Catalog, k: int, liked, c: int = 3,
 
     k : 1 .. 512. liked, exclude : the list forms ``score_topk`` takes. Errors as
     ``cluster_liked``'s."""
-    _check_catalog(catalog)
+    require_whole_catalog(catalog, "multi-interest search needs the liked rows on one device")
     c = _check_c(c)
     k = int(k)
     if not 1 <= k <= _lib.EBT_INTEREST_K_MAX:

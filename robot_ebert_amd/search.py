@@ -154,14 +154,11 @@ def check_weights(off: np.ndarray, w: np.ndarray) -> np.ndarray:
     return W
 
 
-def csr_from_weighted_lists(lists: Sequence[Sequence[int]], weights: Sequence[Sequence[float]],
-                            device, stager=None, check: bool = True
-                            ) -> Tuple[SortedCSR, torch.Tensor]:
-    """csr_from_lists for liked rows with one weight per entry (ebert.h 0.8.0): the same CSR,
-    and the weights as a device float64 [nnz] in the CSR's order (each list is sorted by row,
-    stably, and its weights move with it). Checked here, EbertError naming the query: a weights
-    list of another length than its liked list, a non-finite weight, sum |w| == 0. The CSR's
-    ``weights_checked`` is set: with ``checked_for`` the C entry reads nothing back."""
+def parse_weight_lists(lists: Sequence[Sequence[int]], weights: Sequence[Sequence[float]]
+                       ) -> Tuple[list, list]:
+    """Per-query host weight lists against their liked lists, in the caller's order: (rows int64,
+    weights float64) arrays per query. EbertError naming the query for a weights list that is no
+    list of numbers or has another length than its liked list."""
     if len(weights) != len(lists):
         raise EbertError(f"{len(weights)} weight lists for {len(lists)} liked lists")
     segs, ws = [], []
@@ -173,9 +170,38 @@ def csr_from_weighted_lists(lists: Sequence[Sequence[int]], weights: Sequence[Se
             raise EbertError(f"liked weights of query {b}: {e}") from None
         if x.size != r.size:
             raise EbertError(f"query {b} has {x.size} weights for {r.size} liked rows")
-        o = np.argsort(r, kind="stable")
-        segs.append(r[o])
-        ws.append(x[o])
+        segs.append(r)
+        ws.append(x)
+    return segs, ws
+
+
+def device_liked_weights(liked_weights, nnz: int) -> torch.Tensor:
+    """A caller's weights for a device liked CSR of nnz rows: a device float64 [nnz] tensor,
+    returned contiguous."""
+    if not isinstance(liked_weights, torch.Tensor):
+        raise EbertError("with a device CSR, liked_weights must be a device float64 [nnz] "
+                         "tensor")
+    require_cuda(liked_weights, "liked_weights")
+    if liked_weights.dtype != torch.float64 or liked_weights.dim() != 1 \
+            or liked_weights.numel() != nnz:
+        raise EbertError(f"liked_weights must be float64 [{nnz}] (one per "
+                         f"liked row), got {liked_weights.dtype} "
+                         f"{tuple(liked_weights.shape)}")
+    return liked_weights.contiguous()
+
+
+def csr_from_weighted_lists(lists: Sequence[Sequence[int]], weights: Sequence[Sequence[float]],
+                            device, stager=None, check: bool = True
+                            ) -> Tuple[SortedCSR, torch.Tensor]:
+    """csr_from_lists for liked rows with one weight per entry (ebert.h 0.8.0): the same CSR,
+    and the weights as a device float64 [nnz] in the CSR's order (each list is sorted by row,
+    stably, and its weights move with it). Checked here, EbertError naming the query: a weights
+    list of another length than its liked list, a non-finite weight, sum |w| == 0. The CSR's
+    ``weights_checked`` is set: with ``checked_for`` the C entry reads nothing back."""
+    segs, ws = parse_weight_lists(lists, weights)
+    order = [np.argsort(r, kind="stable") for r in segs]
+    segs = [r[o] for r, o in zip(segs, order)]
+    ws = [x[o] for x, o in zip(ws, order)]
     csr = csr_from_lists(segs, device, stager)   # (sorted already: np.sort leaves them as they are)
     flat = np.concatenate(ws) if ws else np.zeros(0)
     off = np.zeros(len(segs) + 1, dtype=np.int64)
@@ -196,16 +222,7 @@ def _liked_with_weights(liked, liked_weights, dev):
     if liked is None:
         raise EbertError("liked_weights= weighs liked rows: pass liked= (dense queries take none)")
     if isinstance(liked, tuple):
-        if not isinstance(liked_weights, torch.Tensor):
-            raise EbertError("with a device CSR, liked_weights must be a device float64 [nnz] "
-                             "tensor")
-        require_cuda(liked_weights, "liked_weights")
-        if liked_weights.dtype != torch.float64 or liked_weights.dim() != 1 \
-                or liked_weights.numel() != liked[1].numel():
-            raise EbertError(f"liked_weights must be float64 [{int(liked[1].numel())}] (one per "
-                             f"liked row), got {liked_weights.dtype} "
-                             f"{tuple(liked_weights.shape)}")
-        return liked, liked_weights.contiguous()
+        return liked, device_liked_weights(liked_weights, int(liked[1].numel()))
     if isinstance(liked_weights, torch.Tensor):
         raise EbertError("with host liked lists, liked_weights must be host lists parallel to "
                          "them")

@@ -64,6 +64,8 @@ def lib():
     h.ebt_cosine_topk_sharded.argtypes = [ctypes.POINTER(Catalog), ctypes.POINTER(Comm), VP,
                                           ctypes.c_int, I64, I64, VP, VP, I32, VP, VP, VP, VP, SZ,
                                           VP, VP, VP, VP]
+    h.ebt_cosine_topk_weighted.argtypes = h.ebt_cosine_topk.argtypes + [VP, VP]
+    h.ebt_cosine_topk_sharded_weighted.argtypes = h.ebt_cosine_topk_sharded.argtypes + [VP]
     h.ebt_cosine_topk_sharded_submit.argtypes = [
         ctypes.POINTER(Catalog), ctypes.POINTER(Comm), VP, ctypes.c_int, I64, I64, VP, VP, I32,
         VP, VP, VP, VP, SZ, VP, VP, VP, ctypes.POINTER(ShardedPending), VP, VP]
@@ -100,8 +102,9 @@ STAGE_RESCORE = 4   # EBT_STAGE_RESCORE
 
 
 def run_ranks(lib, hip, full, world, k, q=None, liked=None, excl=None, fail_rank=-1,
-              allreduce=False, opt=None, timer=False):
+              allreduce=False, opt=None, timer=False, w=None):
     """ebt_cosine_topk_sharded on `world` thread ranks; returns per-rank (rc, message, s, r).
+    w: the liked rows' weights (device float64, parallel to the rows): the _weighted entry.
     allreduce: the comm also offers all_reduce_f64 (a barrier exchange summing in rank order).
     timer: every rank passes an ebt_timer of its own and queries its rescore stage afterwards;
     a third value is returned, per rank (query rc, total ms, launches)."""
@@ -169,10 +172,11 @@ def run_ranks(lib, hip, full, world, k, q=None, liked=None, excl=None, fail_rank
         eo, er = excl if excl is not None else (None, None)
         tm = lib.ebt_timer_create() if timer else None
         assert tm or not timer
-        rc = lib.ebt_cosine_topk_sharded(
-            ctypes.byref(cat), ctypes.byref(comm), P(q), CODE[q.dtype] if q is not None else 0, B,
-            q.stride(0) if q is not None else 0, P(lo), P(lr), k, P(eo), P(er), optp, P(ws), need,
-            P(s), P(rr), tm, torch.cuda.current_stream(dev).cuda_stream)
+        args = (ctypes.byref(cat), ctypes.byref(comm), P(q), CODE[q.dtype] if q is not None else 0,
+                B, q.stride(0) if q is not None else 0, P(lo), P(lr), k, P(eo), P(er), optp, P(ws),
+                need, P(s), P(rr), tm, torch.cuda.current_stream(dev).cuda_stream)
+        rc = lib.ebt_cosine_topk_sharded(*args) if w is None \
+            else lib.ebt_cosine_topk_sharded_weighted(*args, P(w))
         msg = lib.ebt_last_error().decode() if rc else ""
         if timer:
             ms, launches = ctypes.c_double(-1.0), I64(-1)
@@ -491,3 +495,53 @@ def test_sharded_capi_liked_all_reduce(cuda_device, lib, hip):
     need_g = lib.ebt_sharded_workspace_bytes(ctypes.byref(cat), ctypes.byref(g), 4096, k, None)
     need_r = lib.ebt_sharded_workspace_bytes(ctypes.byref(cat), ctypes.byref(g2), 4096, k, None)
     assert need_g - need_r >= world * 4096 * d * 8
+
+
+@pytest.mark.parametrize("allreduce", [False, True])
+@pytest.mark.parametrize("weighted", [False, True])
+def test_sharded_capi_liked_shard_skip(cuda_device, lib, hip, weighted, allreduce):
+    """The liked sums' shard skip (rows outside the shard add nothing) at the smallest size: 2
+    ranks of 256 rows, d = 64, f32, three users. User 0's liked rows all lie on rank 1 (rank 0
+    skips every one), user 2's single row is rank 0's last (rank 1 skips it), user 1 has two
+    rows on rank 0 and one on rank 1. No user has two rows after a shard boundary, so the
+    shards' partial sums add up in the single catalog's order: every rank's scores and rows are
+    bitwise those of the single-catalog call on the whole matrix, with and without weights,
+    through the all-gather and through all_reduce_f64."""
+    n, d, k, world = 512, 64, 10, 2
+    dev = cuda_device
+    full = torch.from_numpy(gaussian(271, n, d, "f32").astype(np.float32)).to(dev)
+    liked = [[300, 411, 500], [3, 100, 300], [255]]
+    # what makes bitwise equality valid: after the first shard that holds any of a user's rows,
+    # every shard holds at most one (the rank-order sum of the partial sums is then the
+    # sequential sum over the sorted list)
+    cuts = shard_cuts(n, world)
+    for rows_b in liked:
+        per = [sum(cuts[r] <= x < cuts[r + 1] for x in rows_b) for r in range(world)]
+        first = next(r for r in range(world) if per[r])
+        assert rows_b == sorted(rows_b) and all(c <= 1 for c in per[first + 1:]), (rows_b, per)
+    lk = csr(liked, dev)
+    w = torch.tensor([2.0, -0.75, 1.5, -3.0, 0.5, 1.25, -2.5], dtype=torch.float64,
+                     device=dev) if weighted else None
+    out = run_ranks(lib, hip, full, world, k, liked=lk, allreduce=allreduce, w=w)
+    res, calls = out[0], out[1]
+    if allreduce:
+        assert out[2] == [1] * world       # the partial sums
+    else:
+        assert calls[0] == calls[1] >= 1   # (their all-gather among them)
+    cat, state = make_catalog(lib, full)
+    B = len(liked)
+    need = lib.ebt_workspace_bytes(ctypes.byref(cat), B, k, None)
+    assert need > 0
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    s1 = torch.empty((B, k), dtype=torch.float64, device=dev)
+    r1 = torch.empty((B, k), dtype=torch.int64, device=dev)
+    rc = lib.ebt_cosine_topk_weighted(ctypes.byref(cat), None, 0, B, 0, P(lk[0]), P(lk[1]), k,
+                                      None, None, None, P(ws), need, P(s1), P(r1), None,
+                                      torch.cuda.current_stream(dev).cuda_stream, None, P(w))
+    assert rc == 0, lib.ebt_last_error()
+    s1, r1 = s1.cpu().numpy(), r1.cpu().numpy()
+    assert (r1 >= 0).all() and np.isfinite(s1).all()
+    for rank, (rc, msg, s, r) in enumerate(res):
+        assert rc == 0, (rank, msg)
+        np.testing.assert_array_equal(r, r1)
+        assert s.tobytes() == s1.tobytes(), rank

@@ -148,6 +148,60 @@ def test_query_liked_wsum_bitwise(cuda_device, dt, d):
         assert got_s.tobytes() == got.tobytes()
 
 
+def _sum(L, xt, d, ld, g, off, rows, dev):
+    B = off.numel() - 1
+    q64 = torch.full((B, d), float("nan"), dtype=torch.float64, device=dev)
+    L.call("ebt_query_liked_sum", L.ptr(xt), L.DTYPE_CODE[xt.dtype], d, ld, L.ptr(g), B,
+           L.ptr(off), L.ptr(rows), L.ptr(q64), L.stream_of(dev))
+    return q64
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16", "f16", "f64"])
+@pytest.mark.parametrize("d", [77, 768])
+def test_query_liked_sum_bitwise(cuda_device, dt, d):
+    """ebt_query_liked_sum itself (above it is pinned only through "weights of 1.0 give its
+    bits") against a float64 numpy loop in the same order, acc = acc + x / g in CSR order:
+    d = 77 runs the element form, 768 the 16-byte-chunk form; lists with duplicates, a
+    zero-norm row. On the aligned input the element form (the same values at row stride d + 1)
+    gives the chunk form's bits."""
+    ebt, L = _ebt()
+    dev = cuda_device
+    n = 2000
+    x = gaussian(63, n, d, dt)
+    x[3] = 0.0                                    # a zero-norm row (norm guard 1.0)
+    xt = _t(x, dt, dev)
+    g = torch.empty(n, dtype=torch.float64, device=dev)
+    L.call("ebt_row_norms", L.ptr(xt), L.DTYPE_CODE[xt.dtype], n, d, d, L.ptr(g), None,
+           L.stream_of(dev))
+    rng = np.random.default_rng(64)
+    lists = [rng.integers(0, n, size=m) for m in LENS]      # with replacement: duplicates
+    lists[1][0] = 3
+    lists[6][:2] = lists[6][2]                               # and a certain one
+    off_np = np.zeros(len(LENS) + 1, dtype=np.int64)
+    off_np[1:] = np.cumsum(LENS)
+    off = torch.from_numpy(off_np).to(dev)
+    rows = torch.from_numpy(np.concatenate(lists)).to(dev)
+    got = _sum(L, xt, d, d, g, off, rows, dev).cpu().numpy()
+    g_np = g.cpu().numpy()
+    assert g_np[3] == 1.0
+    x64 = xt.to(torch.float64).cpu().numpy()
+    want = np.zeros((len(LENS), d))
+    for b, rl in enumerate(lists):
+        acc = np.zeros(d)
+        for r in rl:
+            acc = acc + x64[r] / g_np[r]
+        want[b] = acc
+    assert got.tobytes() == want.tobytes()
+    if d != 77:
+        # the same values at row stride d + 1 elements: not 16-byte rows, the element form
+        es = xt.element_size()
+        assert (d * es) % 16 == 0 and ((d + 1) * es) % 16 != 0
+        xp = torch.zeros((n, d + 1), dtype=xt.dtype, device=dev)
+        xp[:, :d] = xt
+        got_s = _sum(L, xp, d, d + 1, g, off, rows, dev).cpu().numpy()
+        assert got_s.tobytes() == got.tobytes()
+
+
 # ------------------------------------------------------------ 2. invariants of score_topk ----
 @pytest.fixture(scope="module")
 def c1(cuda_device):

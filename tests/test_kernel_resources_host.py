@@ -15,8 +15,8 @@ from robot_ebert_amd import _lib
 
 READELF = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-readelf")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-KEY_RX = re.compile(r"^    \.(name|private_segment_fixed_size|vgpr_count|agpr_count|"
-                    r"vgpr_spill_count|sgpr_spill_count):\s+(\S+)\s*$")
+KEY_RX = re.compile(r"^    \.(name|private_segment_fixed_size|group_segment_fixed_size|vgpr_count|"
+                    r"agpr_count|vgpr_spill_count|sgpr_spill_count):\s+(\S+)\s*$")
 
 
 def _gfx950_code_objects(path):
